@@ -1,6 +1,18 @@
 """HL-HGAT training throughput on MI355X (BASELINE.json metric, config 2).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--eager]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds
+the batches and the model, runs W warm-up steps, times exactly K steps, writes
+the last timed step's results if `--dump-outputs DIR` is given (the loss the
+step returned and the training state it left, `DIR/<name>.npy`, float32; the
+inputs and the initial weights are seeded, so two builds can be compared
+array for array) and prints one short JSON line.  `--full` adds every other
+leg to that line: the parity check against the oracle, the kernel rooflines
+(stamped eager pass, rocprofv3 child), the config-5 SpMM, the H2D, eval and
+loader legs, the CPU oracle baseline and the configs 3-5 heads; the `--no-*`
+options drop single legs of a `--full` run.
 
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (RANK set)
 every rank runs the step directly; run plainly, `--gpus N` starts the N ranks
@@ -21,9 +33,10 @@ times that host work.
 Inputs are resident in HBM before the timed region (8 distinct batches,
 rotated, padded to one capacity bucket).  The step runs as ONE replayed
 hipGraph for every batch of the bucket (hlhgat.train.TrainStep +
-hodge_dataset.pad_batch; --eager runs it op by op).  After the timed region
-a short eager pass with hipExtLaunchKernel event stamps on the SpMM and the
-projection kernels gives the roofline figures.  Rank 0 prints one JSON line.
+hodge_dataset.pad_batch; --eager runs it op by op).  With --full, after the
+timed region a short eager pass with hipExtLaunchKernel event stamps on the
+SpMM and the projection kernels gives the roofline figures.  Rank 0 prints one
+JSON line.
 """
 from __future__ import annotations
 
@@ -34,12 +47,6 @@ import socket
 import subprocess
 import sys
 import time
-
-# A launcher setting, not a product one (the package sets nothing in the
-# process environment): the replayed step's hipGraph on two hardware queues
-# instead of the runtime's four (2.74 -> 2.68 ms per step).
-# Read at HIP init; a value set by the user wins.
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "2")
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 for p in (REPO, os.path.join(REPO, "hl-hgat_amd")):
@@ -59,6 +66,39 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+# worker processes generating the synthetic graphs (set by main(): only when
+# this file is the program, so that a spawned worker re-imports nothing else)
+GEN_PROCS = 1
+
+
+def _zinc_chunk(seeds):
+    """Pool worker: the graphs of `seeds` as plain dicts of numpy arrays (a
+    tensor would travel as a shared-memory handle each)."""
+    from hlhgat.synthetic import zinc_like_graph
+    torch.set_num_threads(1)
+    return [{k: v.numpy() if torch.is_tensor(v) else v
+             for k, v in vars(zinc_like_graph(s, 15)).items()} for s in seeds]
+
+
+def zinc_graphs(seeds):
+    """zinc_like_graph(s, 15) for every seed, in order.  Each graph is a
+    function of its own seed alone, so GEN_PROCS spawned CPU workers (they
+    never touch the GPU) build the same graphs, bit for bit, as the serial
+    loop; 8000 graphs take ~20 s of Python on one core."""
+    import numpy as np
+    from hlhgat.hodge_dataset import PairData
+    from hlhgat.synthetic import zinc_like_graph
+    if GEN_PROCS <= 1 or len(seeds) < 512:
+        return [zinc_like_graph(s, 15) for s in seeds]
+    import multiprocessing as mp
+    chunks = [seeds[i:i + 125] for i in range(0, len(seeds), 125)]
+    with mp.get_context("spawn").Pool(GEN_PROCS) as pool:
+        parts = pool.map(_zinc_chunk, chunks, chunksize=1)
+    return [PairData(**{k: torch.from_numpy(v) if isinstance(v, np.ndarray) else v
+                        for k, v in d.items()})
+            for part in parts for d in part]
+
+
 def make_batches(n_batches, rank, device, quantum=512, caps=None):
     """n_batches distinct synthetic 1000-graph batches, padded to ONE capacity
     bucket (the max of their static_caps) so that a single captured hipGraph
@@ -69,9 +109,8 @@ def make_batches(n_batches, rank, device, quantum=512, caps=None):
     collate + pad_batch, tests/test_host.py)."""
     import numpy as np
     from hlhgat.hodge_dataset import PackedGraphs
-    from hlhgat.synthetic import zinc_like_graph
-    graphs = [zinc_like_graph((1 + rank * 101 + i) * 1_000_003 + j, 15)
-              for i in range(n_batches) for j in range(GRAPHS_PER_GPU)]
+    graphs = zinc_graphs([(1 + rank * 101 + i) * 1_000_003 + j
+                          for i in range(n_batches) for j in range(GRAPHS_PER_GPU)])
     ds = PackedGraphs(graphs, check_hodge=False)
     idxs = [np.arange(i * GRAPHS_PER_GPU, (i + 1) * GRAPHS_PER_GPU) for i in range(n_batches)]
     if caps is None:
@@ -896,6 +935,40 @@ def heads_leg(device, steps=8, warmup=2, n_batches=8, cpu_budget_s=8.0):
     return out
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, step, loss):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, one
+    float32 `DIR/<name>.npy` each -- `loss` (the value TrainStep returned) and
+    the training state the step left: `params` and `grads` (TrainStep's flat
+    parameter and gradient buckets, in model.parameters() order), the Adam
+    moments, and `buffers` (the module's floating-point buffers, the BatchNorm
+    running statistics, concatenated in named_buffers() order).  An array that
+    would take the dump past DUMP_BYTES is cut to a fixed, seeded sample of
+    its elements (ascending indices)."""
+    import numpy as np
+    if step.device.type == "cuda":
+        torch.cuda.synchronize()
+    out = {"loss": loss.detach().reshape(-1), "params": step.flat, "grads": step.flat_grad}
+    state = step.opt.state.get(step.master, {})
+    for k in ("exp_avg", "exp_avg_sq"):
+        if torch.is_tensor(state.get(k)):
+            out["adam_" + k] = state[k]
+    bufs = [b.detach().reshape(-1).float() for _, b in step.model.named_buffers()
+            if b.is_floating_point()]
+    if bufs:
+        out["buffers"] = torch.cat(bufs)
+    os.makedirs(path, exist_ok=True)
+    room = DUMP_BYTES // (4 * len(out))  # elements per array
+    for name, t in out.items():
+        a = t.detach().reshape(-1).float().cpu().numpy()
+        if a.size > room:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, room, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[rank 0] outputs of the last timed step written to {path}: {', '.join(out)}")
+
+
 WORKLOADS = {"cfg2": None, "cfg3": "cfg3_cifar_attpool", "cfg4": "cfg4_pepfunc_attpool",
              "cfg5": "cfg5_tsp_pyr"}
 
@@ -951,13 +1024,16 @@ def head_workload(args, rank, world, device):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for i in range(args.steps):
-        step(padded[i % len(padded)])
+        loss = step(padded[i % len(padded)])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, device)
     hlhgat.ops.check_device_errors()
+    if rank == 0 and args.dump_outputs and loss is not None:
+        dump_outputs(args.dump_outputs, step, loss)
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         print(json.dumps({
@@ -1093,6 +1169,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--batches", type=int, default=8)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (loss, parameters, gradients, "
+                         "Adam moments, BatchNorm buffers) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (parity check, "
+                         "rooflines, config-5 SpMM, H2D, eval, loader, CPU baseline, configs "
+                         "3-5 heads); the --no-* options below drop single legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--loader-workers", type=int, default=4,
                     help="GraphLoader collation threads (the reference's num_workers=4)")
@@ -1137,7 +1220,10 @@ def main():
     if args.dry_run:
         return dry_run(args)
     if args.replay_probe:
-        return replay_probe(args)
+        return replay_probe(args)  # under the profiler: no worker processes to trace
+    global GEN_PROCS  # CPU workers for the synthetic graphs, shared between the ranks
+    if not any(k.startswith("ROCPROF") for k in os.environ):  # (rocprofv3 would trace them too)
+        GEN_PROCS = max(1, min(12, os.cpu_count() or 1) // args.gpus)
 
     from hlhgat.distributed import init_distributed, max_over_ranks
     rank, world, device = init_distributed("nccl")  # RCCL over xGMI; one process per GPU
@@ -1156,7 +1242,7 @@ def main():
     torch.manual_seed(0)
     model = hlhgat.HL_HGCNN_zinc_dense_int3_pyr(**MODEL_KW).to(device).train()
     pcheck = None
-    if rank == 0 and not args.no_parity_check:
+    if rank == 0 and args.full and not args.no_parity_check:
         pcheck = parity_check(model, batches[0], raw0)
         log(f"[rank 0] parity check vs oracle (1000 graphs): {pcheck['max_rel_err']:.2e}")
     crit = hlhgat.nn.L1Loss()  # torch.nn.L1Loss, one HIP launch each way
@@ -1177,8 +1263,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for i in range(args.steps):
-        step(batches[i % len(batches)])
+        loss = step(batches[i % len(batches)])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1186,43 +1273,11 @@ def main():
     elapsed = max_over_ranks(elapsed, device)
     ops.check_device_errors()  # a kernel that reported unusable results voids the run
     giveups_timed = ops.bn_giveups()["count"]
+    if rank == 0 and args.dump_outputs and loss is not None:
+        dump_outputs(args.dump_outputs, step, loss)  # before any later leg trains on
 
-    # roofline pass: eager steps, SpMM / projection / BatchNorm launches event-stamped
-    L = hlhgat._lib
-    classes = (*POLY_CLASSES, "PROF_GATHER2", "PROF_PROJ", "PROF_PROJ_BWD", "PROF_PROJ_BN",
-               "PROF_BN_FWD", "PROF_BN_BWD")
-    ops.prof_reset()
-    prof_enable_all(L, classes, True)
-    for i in range(args.prof_steps):
-        step._eager(batches[i % len(batches)])
-    torch.cuda.synchronize()
-    prof_enable_all(L, classes, False)
-    ops.check_device_errors()
-
-    poly = prof_sum(L, POLY_CLASSES)
-    proj = ops.prof_read(L.PROF_PROJ)
     ms_step = elapsed / args.steps * 1e3
     value = world * GRAPHS_PER_GPU * args.steps / elapsed
-
-    def gbs(p):
-        return p["bytes"] / (p["ms"] * 1e-3) / 1e9 if p["ms"] > 0 else 0.0
-
-    poly_gbs = gbs(poly)
-    traffic, traffic_src = pmc_traffic("k_poly_step")
-    roofline = {
-        "kernel": "k_poly_step (CSR SpMM / fused Laguerre step over L0 and L1, fwd + adjoint, "
-                  "and the NodeEdgeInt |B1| gathers)",
-        "measured": f"hipExtLaunchKernel start/stop stamps, {args.prof_steps} eager steps after "
-                    f"the timed region",
-        "bound": "hbm", "achieved": round(poly_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(poly_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
-        "traffic_source": traffic_src,
-        "launches": poly["launches"],
-        "avg_launch_us": round(poly["ms"] * 1e3 / max(poly["launches"], 1), 2),
-        "algorithmic_bytes_per_launch": round(poly["bytes"] / max(poly["launches"], 1)),
-        # per call site, per eager step: launches, time, algorithmic bytes
-        "call_sites": {nm: _site(prof_sum(L, c), args.prof_steps) for nm, c in POLY_SITES},
-    }
     result = {
         "metric": METRIC,
         "value": round(value, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps,
@@ -1244,6 +1299,51 @@ def main():
                    "padding_overhead": round((caps["rows_t"] + caps["rows_s"]) / real_rows - 1, 4),
                    "graphs_per_gpu": GRAPHS_PER_GPU, "global_batch": world * GRAPHS_PER_GPU,
                    "parallelism": f"dp{world}"},
+    }
+    if not args.full:
+        # the plain run: the headline figure alone (every other leg: --full)
+        if rank == 0:
+            result["bn_barrier"] = {"giveups_timed_region": giveups_timed, "wait_us": 1000}
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # roofline pass: eager steps, SpMM / projection / BatchNorm launches event-stamped
+    L = hlhgat._lib
+    classes = (*POLY_CLASSES, "PROF_GATHER2", "PROF_PROJ", "PROF_PROJ_BWD", "PROF_PROJ_BN",
+               "PROF_BN_FWD", "PROF_BN_BWD")
+    ops.prof_reset()
+    prof_enable_all(L, classes, True)
+    for i in range(args.prof_steps):
+        step._eager(batches[i % len(batches)])
+    torch.cuda.synchronize()
+    prof_enable_all(L, classes, False)
+    ops.check_device_errors()
+
+    poly = prof_sum(L, POLY_CLASSES)
+    proj = ops.prof_read(L.PROF_PROJ)
+
+    def gbs(p):
+        return p["bytes"] / (p["ms"] * 1e-3) / 1e9 if p["ms"] > 0 else 0.0
+
+    poly_gbs = gbs(poly)
+    traffic, traffic_src = pmc_traffic("k_poly_step")
+    roofline = {
+        "kernel": "k_poly_step (CSR SpMM / fused Laguerre step over L0 and L1, fwd + adjoint, "
+                  "and the NodeEdgeInt |B1| gathers)",
+        "measured": f"hipExtLaunchKernel start/stop stamps, {args.prof_steps} eager steps after "
+                    f"the timed region",
+        "bound": "hbm", "achieved": round(poly_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(poly_gbs / HBM_PEAK_GBS, 4), "traffic": traffic,
+        "traffic_source": traffic_src,
+        "launches": poly["launches"],
+        "avg_launch_us": round(poly["ms"] * 1e3 / max(poly["launches"], 1), 2),
+        "algorithmic_bytes_per_launch": round(poly["bytes"] / max(poly["launches"], 1)),
+        # per call site, per eager step: launches, time, algorithmic bytes
+        "call_sites": {nm: _site(prof_sum(L, c), args.prof_steps) for nm, c in POLY_SITES},
+    }
+    result.update({
         "roofline": roofline,
         "cpu_baseline": None,
         "parity_check": pcheck,
@@ -1267,7 +1367,7 @@ def main():
         "eval": None,
         "h2d": None,
         "loader": None,
-    }
+    })
     result_eager_rooflines = dict(result["rooflines"])
     if rank == 0:
         roofline["isolated"] = isolated_poly_step(device, batches[0])

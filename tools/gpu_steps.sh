@@ -6,7 +6,7 @@
 #   bn      the BatchNorm barrier tests (hand-over, CU hog, bitwise)
 #   tests   the whole GPU suite
 #   smoke   __graft_entry__.smoke()
-#   bench   the default bench line (driver command)
+#   bench   the bench line with every leg (bench.py --full)
 #   pmcstep the config-2 step under rocprofv3 --pmc (serialised dispatch)
 #   prof    rocprofv3 kernel stats + step census of the replayed bench
 #   pmc     FETCH / WRITE passes for the roofline traffic
@@ -44,7 +44,7 @@ for s in "$@"; do
     bn) step bn 600 $PT tests/test_gpu_parity.py -m gpu -v -s -k "bn_ or proj_bn or handover or hog" ;;
     tests) step tests 1100 $PT tests -m gpu -q ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 900 python bench.py ;;
+    bench) step bench 900 python bench.py --full ;;
     pmcstep) rm -rf gpurun_out/${TAG}_pmcstep_d
              step pmcstep 200 timeout -s KILL 180 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d gpurun_out/${TAG}_pmcstep_d -o p --output-format csv -- python3 tools/probes/poly_context.py --steps 3
              rm -rf gpurun_out/${TAG}_pmcstep_d ;;
@@ -87,9 +87,9 @@ for s in "$@"; do
          rm -rf gpurun_out/pmcf gpurun_out/pmcw
          # the bench reads the newest profiles/*_pmc_traffic.json: this round's
          cp gpurun_out/${TAG}_pmc_traffic.json profiles/r06_pmc_traffic.json || true ;;
-    census) step census 900 python3 bench.py --no-cpu-baseline --no-loader --no-parity-check --steps 20
+    census) step census 900 python3 bench.py --full --no-cpu-baseline --no-loader --no-parity-check --steps 20
           python3 tools/poly_census.py gpurun_out/${TAG}_census.log > gpurun_out/${TAG}_poly_census.txt || true ;;
-    census1) HLHGAT_STREAM_FORK=0 step census1 900 python3 bench.py --no-cpu-baseline --no-loader --no-parity-check --no-replay-census --steps 10
+    census1) HLHGAT_STREAM_FORK=0 step census1 900 python3 bench.py --full --no-cpu-baseline --no-loader --no-parity-check --no-replay-census --steps 10
           python3 tools/poly_census.py gpurun_out/${TAG}_census1.log > gpurun_out/${TAG}_poly_census_1stream.txt || true ;;
     fcalib) rm -rf gpurun_out/${TAG}_fc
           step fcalib 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/${TAG}_fc -o f --output-format csv -- python3 tools/probes/fetch_calib.py run --meta gpurun_out/${TAG}_fc_meta.json
@@ -139,7 +139,7 @@ for s in "$@"; do
            grep -o '"ms_per_step": [0-9.]*' gpurun_out/${TAG}_abw_${w}_${o}_$r.log | sed "s/^/$w ops=$o rounds=$r /" >> gpurun_out/${TAG}_abw.txt || true
          done; done ;;
     abload) for d in 2 3 4 2 3 4; do
-           step abload_$d 400 python3 bench.py --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --loader-depth $d
+           step abload_$d 400 python3 bench.py --full --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --loader-depth $d
            python3 -c "import json,sys; r=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{\"metric')][-1]; L=r['loader']; print('depth', sys.argv[2], r['ms_per_step'], L['loader_fed']['ms_per_step'], round(r['ms_per_step']/L['loader_fed']['ms_per_step'],3), L['loader_fed']['host_ms_per_step'])" gpurun_out/${TAG}_abload_$d.log $d >> gpurun_out/${TAG}_abload.txt || true
          done ;;
     abbn) for r in 1 2; do for v in 128 64 256 512; do
@@ -160,7 +160,7 @@ for s in "$@"; do
          done; done ;;
     abload9) for r in 1 2; do for v in base host hostsl4 devsl4; do
            case $v in base) E=""; A="";; host) E="HLHGAT_STAGE_WAIT=host"; A="";; hostsl4) E="HLHGAT_STAGE_WAIT=host"; A="--loader-slots 4";; devsl4) E=""; A="--loader-slots 4";; esac
-           step abload9_${v}_$r 400 env $E python3 bench.py --no-heads --no-cpu-baseline --no-replay-census $A
+           step abload9_${v}_$r 400 env $E python3 bench.py --full --no-heads --no-cpu-baseline --no-replay-census $A
            python3 -c "import json,sys; r=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{\"metric')][-1]; L=r['loader']['loader_fed']; print(sys.argv[2], r['ms_per_step'], L['ms_per_step'], round(r['ms_per_step']/L['ms_per_step'],3), L['host_ms_per_step'], L.get('feeder_ms_per_batch'), L.get('stage_ms_per_batch'))" gpurun_out/${TAG}_abload9_${v}_$r.log $v >> gpurun_out/${TAG}_abload9.txt || true
          done; done ;;
     abopsf) for r in 1 2; do for w in cfg5 cfg3; do for o in x f; do

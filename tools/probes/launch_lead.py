@@ -16,7 +16,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 for p in (REPO, os.path.join(REPO, "hl-hgat_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "2")
 
 import torch  # noqa: E402
 
