@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("HLHGAT_LIB", os.path.join(_HERE, "libhlhgat.so"))
 c_i32, c_i64, c_f32, c_f64, c_vp, c_sz = (C.c_int32, C.c_int64, C.c_float,
                                            C.c_double, C.c_void_p, C.c_size_t)
 P_i64 = C.POINTER(c_i64)
+P_i32 = C.POINTER(c_i32)
 P_f64 = C.POINTER(c_f64)
 P_vp = C.POINTER(c_vp)
 
@@ -166,6 +167,22 @@ SIGNATURES = {
     "hlhgat_prof_reset": (c_i32, []),
     "hlhgat_prof_read": (c_i32, [c_i32, P_i64, P_f64, P_f64, P_f64]),
     "hlhgat_graph_kernel_count": (c_i32, [c_vp, C.c_char_p, P_i64, P_i64]),
+    "hlhgat_tconv_pack": (c_i32, [c_i32, P_vp, P_i64, P_i32, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "hlhgat_tconv_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64,
+                                 c_i64, c_vp, c_vp]),
+    "hlhgat_tconv_embed_fwd": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp,
+                                       c_vp]),
+    "hlhgat_tconv_bwd_weight_workspace_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i32]),
+    "hlhgat_tconv_bwd_weight": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                        P_vp, P_i64, P_i32, c_vp, c_vp, c_i64, c_vp]),
+    "hlhgat_maxpool_time_len": (c_i64, [c_i64, c_i32]),
+    "hlhgat_leaky_maxpool_time_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp,
+                                              c_vp, c_vp]),
+    "hlhgat_leaky_maxpool_time_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32,
+                                              c_f32, c_vp, c_vp]),
+    "hlhgat_time_readout_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "hlhgat_time_readout_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp,
+                                        c_vp]),
 }
 
 # constants from include/hlhgat.h

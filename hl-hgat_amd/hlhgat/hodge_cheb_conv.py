@@ -10,6 +10,9 @@ arithmetic runs in the HIP kernels of libhlhgat.so (see ops.py):
                                            fused attention score
   HL_filter          (:117-188)  block composition
   SAPool             (:36-59)    attention-scaled cluster pooling
+  Inception1D        (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:474-515)  temporal
+                     front end: implicit-GEMM convolutions over time, fused
+                     LeakyReLU + max-pool and LeakyReLU + max|mean readout
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ from .hodge_dataset import BoundaryOperator, adj2par1, boundary_from_sparse, deg
 from .nn import BatchNorm, Linear, Sequential, run_sequential
 
 __all__ = ["HodgeLaguerreConv", "HodgeChebConv", "NodeEdgeInt", "MSI", "HL_filter", "SAPool",
-           "HodgeLaguerreFastConv"]
+           "HodgeLaguerreFastConv", "Inception1D"]
 
 
 class _HodgePolyConv(nn.Module):
@@ -139,6 +142,11 @@ class HodgeLaguerreFastConv(HodgeLaguerreConv):
     def forward(self, x: Tensor, adj_t, *args, **kwargs) -> Tensor:  # type: ignore[override]
         edge_index, edge_weight = self.adj_to_edge_index(adj_t)
         return super().forward(x, edge_index, edge_weight)
+
+    def forward_bn(self, x: Tensor, adj_t, bn: nn.BatchNorm1d,  # type: ignore[override]
+                   relu: bool) -> Tensor:
+        edge_index, edge_weight = self.adj_to_edge_index(adj_t)
+        return super().forward_bn(x, edge_index, edge_weight, bn=bn, relu=relu)
 
 
 def _sigma_code(sigma: nn.Module) -> int:
@@ -386,3 +394,72 @@ class SAPool(nn.Module):
         D = degree(datas[k].edge_index.view(-1).to(device), num_nodes=x_t0.shape[0]) + 1e-6
         return (x_t0, x_s0, par_1, D, k, edge_index_t, edge_weight_t, edge_index_s,
                 edge_weight_s, att_t, att_s)
+
+
+class Inception1D(nn.Module):
+    """Inception module over fMRI time courses (HL-HGAT-DEMO/lib/
+    Hodge_Cheb_Conv.py:474-515): x [N, T] -> embedding conv (1 -> C, 5 taps) ->
+    three parallel convs (1 | 3 | 5 taps) -> bn1 -> LeakyReLU -> max-pool over
+    time -> three parallel convs -> bn2 -> LeakyReLU, then [max_t | mean_t]
+    ([N, 8*num_channels], ``if_readout``) or the series [N, T', 4*num_channels].
+
+    Same submodules and state_dict as the reference.  On a ROCm device the
+    Conv1d / MaxPool1d modules only hold the parameters: the arithmetic runs
+    channels-last in the HIP kernels of ops.temporal_conv (one launch per
+    stage for the three branches), ops.leaky_maxpool_time and
+    ops.time_readout, the BatchNorms through ops.batch_norm_act on the
+    [N*T, C] view.  CPU tensors take the torch ops."""
+
+    def __init__(self, in_channels=64, num_channels=8, maxpool=3, if_dim_reduction=False,
+                 leaky_slope=0.1, if_readout=False):
+        super().__init__()
+        self.in_channels = in_channels
+        self.num_channels = num_channels
+        self.if_dim_reduction = if_dim_reduction
+        self.if_readout = if_readout
+        self.maxpool = maxpool
+        self.leaky_slope = leaky_slope
+        self.embedding = nn.Conv1d(1, in_channels, 5, padding=2)
+        self.channel1_1 = nn.Conv1d(in_channels, int(in_channels / 4), 1, padding=0)
+        self.channel2_1 = nn.Conv1d(in_channels, int(in_channels / 2), 3, padding=1)
+        self.channel3_1 = nn.Conv1d(in_channels, int(in_channels / 4), 5, padding=2)
+        self.pool_1 = nn.MaxPool1d(maxpool, stride=int(maxpool - 1),
+                                   padding=int((maxpool - 1) / 2))
+        self.channel1_2 = nn.Conv1d(in_channels, num_channels, 1, padding=0)
+        self.channel2_2 = nn.Conv1d(in_channels, num_channels * 2, 3, padding=1)
+        self.channel3_2 = nn.Conv1d(in_channels, num_channels, 5, padding=2)
+        self.leakyReLU = nn.LeakyReLU(leaky_slope)
+        self.bn1 = nn.BatchNorm1d(self.in_channels)
+        self.bn2 = nn.BatchNorm1d(self.num_channels * 4)
+
+    def _stage(self, x: Tensor, convs) -> Tensor:
+        return ops.temporal_conv(x, [c.weight for c in convs], [c.bias for c in convs])
+
+    def _forward_hip(self, x: Tensor) -> Tensor:
+        N, T = x.shape
+        slope = self.leakyReLU.negative_slope
+        h = self._stage(x.reshape(N, T, 1), [self.embedding])
+        h = self._stage(h, [self.channel1_1, self.channel2_1, self.channel3_1])
+        h = ops.batch_norm_act(h.view(N * T, -1), self.bn1, relu=False).view(N, T, -1)
+        h = ops.leaky_maxpool_time(h, slope, self.maxpool)
+        T2 = h.size(1)
+        h = self._stage(h, [self.channel1_2, self.channel2_2, self.channel3_2])
+        h = ops.batch_norm_act(h.view(N * T2, -1), self.bn2, relu=False).view(N, T2, -1)
+        if self.if_readout:
+            return ops.time_readout(h, slope)
+        return torch.nn.functional.leaky_relu(h, slope)
+
+    def forward(self, x: Tensor) -> Tensor:
+        if x.dim() != 2:
+            raise ValueError(f"Inception1D expects [N, T] time courses, got {tuple(x.shape)}")
+        if x.is_cuda:
+            return self._forward_hip(x)
+        x = torch.unsqueeze(x, 1)  # N x C x T
+        x = self.embedding(x)
+        x = torch.cat((self.channel1_1(x), self.channel2_1(x), self.channel3_1(x)), dim=1)
+        x = self.pool_1(self.leakyReLU(self.bn1(x)))
+        x = torch.cat((self.channel1_2(x), self.channel2_2(x), self.channel3_2(x)), dim=1)
+        x = self.leakyReLU(self.bn2(x))
+        if self.if_readout:
+            return torch.cat([x.max(dim=-1)[0], x.mean(dim=-1)], dim=-1)
+        return torch.transpose(x, 1, 2)

@@ -13,7 +13,8 @@ import torch.nn as nn
 from torch.nn import Dropout, Linear
 
 from . import ops
-from .hodge_cheb_conv import HodgeLaguerreConv, NodeEdgeInt, cluster_mean
+from .hodge_cheb_conv import (HodgeLaguerreConv, HodgeLaguerreFastConv, Inception1D, NodeEdgeInt,
+                              cluster_mean)
 from .distributed import global_max
 from .hodge_dataset import adj2par1, degree
 from . import nn as _nn
@@ -23,7 +24,7 @@ __all__ = ["HL_HGCNN_zinc_dense_int3_pyr", "HL_HGCNN_pepfunc_dense_int3_pyr",
            "HL_HGCNN_CIFAR10SP_dense_int3_pyr", "HL_HGCNN_zinc_dense_poolint3_pyr",
            "HL_HGCNN_TSP_dense_int3_pyr", "HL_HGCNN_CIFAR10SP_dense_int3_attpool",
            "HL_HGCNN_zinc_dense_int3_attpool", "HL_HGCNN_pepfunc_dense_int3_attpool",
-           "segment_ptr", "mean_pool_sorted"]
+           "HL_HGAT_attpool", "segment_ptr", "mean_pool_sorted"]
 
 
 def segment_ptr(counts: torch.Tensor, device) -> torch.Tensor:
@@ -790,3 +791,149 @@ class HL_HGCNN_pepfunc_dense_int3_attpool(_AttPoolHead):
 
     def forward(self, datas, device="cuda:0"):
         return super().forward(datas, device)
+
+
+def _demo_block(cin_t, cin_s, cout, K, dropout_ratio, leaky_slope=0.1):
+    """An HL block of the DEMO head (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:
+    267-278): HodgeLaguerreFastConv -> BatchNorm -> LeakyReLU per side."""
+    layers = [(HodgeLaguerreFastConv(cin_t, cout, K=K), "x_t, adj_t -> x_t"),
+              (BatchNorm(cout), "x_t -> x_t"),
+              (nn.LeakyReLU(negative_slope=leaky_slope), "x_t -> x_t"),
+              (Dropout(p=dropout_ratio), "x_t -> x_t"),
+              (HodgeLaguerreFastConv(cin_s, cout, K=K), "x_s, adj_s -> x_s"),
+              (BatchNorm(cout), "x_s -> x_s"),
+              (nn.LeakyReLU(negative_slope=leaky_slope), "x_s -> x_s"),
+              (Dropout(p=dropout_ratio), "x_s -> x_s"),
+              (lambda x1, x2: [x1, x2], "x_t, x_s -> x")]
+    return Sequential("x_t, adj_t, x_s, adj_s", layers)
+
+
+def _uniform_count(counts, what: str) -> int:
+    c = torch.as_tensor(counts).view(-1).tolist()
+    if len(set(int(v) for v in c)) != 1:
+        raise ValueError(f"HL_HGAT_attpool: every graph of a batch must have the same number of "
+                         f"{what} (the head flattens them per graph); got {sorted(set(c))}")
+    return int(c[0])
+
+
+class HL_HGAT_attpool(nn.Module):
+    """The brain-fMRI head of HL-HGAT-DEMO (lib/Hodge_Cheb_Conv.py:250-399):
+    Inception1D over every node's time course, dense NodeEdgeInt + Laguerre
+    blocks with sigmoid node / edge attention and MLGC pooling after the first
+    ``pool_num`` levels, a one-channel readout per node and edge flattened per
+    graph (``num_nodepedge`` = nodes + edges of the last level) and an MLP.
+    Constructor, state_dict and ``forward(datas, device) -> (out, latent,
+    node_att, edge_att)`` as published (HL-HGAT-DEMO/weights/HL_HGAT_Brain.pt
+    loads strictly); ``datas`` = pool_num + 1 levels, level p carrying
+    ``pos_t`` / ``pos_s`` (cluster of each node / edge in level p + 1, inf =
+    dropped).  With pool_num = 0 the attentions are None."""
+
+    def __init__(self, channels=[2, 2, 2], filters=[32, 64, 128], mlp_channels=[], K=4,
+                 node_dim=64, edge_dim=1, num_classes=1, dropout_ratio=0.0,
+                 dropout_ratio_mlp=0.0, pool_num=2, keig=0, num_nodepedge=2089):
+        super().__init__()
+        self.channels = channels
+        self.filters = filters
+        self.mlp_channels = mlp_channels
+        self.node_dim = node_dim + keig
+        self.edge_dim = edge_dim + keig
+        self.initial_channel = self.filters[0]
+        self.pool_loc = [i for i in range(pool_num)]
+        self.node_embedding = Inception1D(if_readout=True)
+        self.keig = keig
+        self.num_nodepedge = num_nodepedge
+        self.HL_init_conv = _demo_block(self.node_dim, self.edge_dim, self.initial_channel, K,
+                                        dropout_ratio)
+        gcn_insize = self.initial_channel
+        final_out = self.initial_channel
+        for i, gcn_outsize in enumerate(self.filters):
+            for j in range(self.channels[i]):
+                setattr(self, "NEInt{}{}".format(i, j), NodeEdgeInt(d=gcn_insize, dv=gcn_outsize))
+                setattr(self, "NEConv{}{}".format(i, j),
+                        _demo_block(gcn_outsize, gcn_outsize, gcn_outsize, K, dropout_ratio))
+                gcn_insize = gcn_insize + gcn_outsize
+                final_out = gcn_outsize
+            if i in self.pool_loc:
+                setattr(self, "NEAtt{}".format(i),
+                        NodeEdgeInt(d=gcn_insize, dv=gcn_outsize, only_att=True,
+                                    sigma=nn.Sigmoid()))
+        self.readout = Sequential("x_t, adj_t, x_s, adj_s", [
+            (HodgeLaguerreFastConv(final_out, 1, K=1), "x_t, adj_t -> x_t"),
+            (HodgeLaguerreFastConv(final_out, 1, K=1), "x_s, adj_s -> x_s"),
+            (lambda x1, x2: [x1, x2], "x_t, x_s -> x")])
+        mlp_insize = self.num_nodepedge
+        for i, mlp_outsize in enumerate(mlp_channels):
+            setattr(self, "mlp%d" % i, nn.Sequential(
+                Linear(mlp_insize, mlp_outsize), nn.BatchNorm1d(mlp_outsize),
+                nn.LeakyReLU(negative_slope=0.1), nn.Dropout(dropout_ratio_mlp)))
+            mlp_insize = mlp_outsize
+        self.out = Linear(mlp_insize, num_classes)
+
+    @staticmethod
+    def _level(d, dev):
+        return d.to(dev) if hasattr(d, "to") else d
+
+    def _mlp(self, seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+        lin, bn, act, drop = seq
+        x = ops.batch_norm_act(ops.linear_blocks([x], lin.weight, lin.bias), bn, relu=False)
+        x = act(x)
+        return x if (drop.p == 0.0 or not drop.training) else drop(x)
+
+    def forward(self, datas, device="cuda:0"):
+        n_pool = len(self.pool_loc)
+        if len(datas) != n_pool + 1:
+            raise ValueError(f"HL_HGAT_attpool: pool_num={n_pool} needs {n_pool + 1} levels in "
+                             f"datas, got {len(datas)}")
+        dev = torch.device(device)
+        datas = [self._level(d, dev) for d in datas]
+        data = datas[0]
+        n_graphs = int(torch.as_tensor(data.num_node1).numel())
+        for p, d in enumerate(datas):
+            _uniform_count(d.num_node1, f"nodes (level {p})")
+            _uniform_count(d.num_edge1, f"edges (level {p})")
+        # global coarse index of every node / edge of level p (:334-343)
+        pos_ts, pos_ss = [], []
+        for p in range(n_pool):
+            d, dn = datas[p], datas[p + 1]
+            pos_ts.append(d.pos_t.to(dev).view(-1).to(torch.float32) + _level_offsets(
+                dn.num_node1, d.num_node1, dev, d.x_t.size(0)))
+            pos_ss.append(d.pos_s.to(dev).view(-1).to(torch.float32) + _level_offsets(
+                dn.num_edge1, d.num_edge1, dev, d.x_s.size(0)))
+        x_t = self.node_embedding(data.x_t.to(dev))
+        x_s = data.x_s.to(dev)
+        adj_t = (data.edge_index_t.to(dev), data.edge_weight_t.to(dev))
+        adj_s = (data.edge_index_s.to(dev), data.edge_weight_s.to(dev))
+        x_t, x_s = self.HL_init_conv(x_t, adj_t, x_s, adj_s)
+        x_t0, x_s0 = x_t, x_s
+        k = 0
+        par_1 = adj2par1(data.edge_index.to(dev), x_t0.shape[0], x_s0.shape[0])
+        D = degree(data.edge_index.to(dev).view(-1), num_nodes=x_t0.shape[0]) + 1e-6
+        node_att = edge_att = None
+        for i, _ in enumerate(self.channels):
+            for j in range(self.channels[i]):
+                x_t, x_s = getattr(self, "NEInt{}{}".format(i, j))(x_t0, x_s0, par_1, D)
+                x_t, x_s = getattr(self, "NEConv{}{}".format(i, j))(x_t, adj_t, x_s, adj_s)
+                x_t0 = torch.cat([x_t0, x_t], dim=-1)
+                x_s0 = torch.cat([x_s0, x_s], dim=-1)
+            if i in self.pool_loc:
+                att_t, att_s = getattr(self, "NEAtt%d" % i)(x_t0, x_s0, par_1, D)
+                if k == 0:
+                    node_att, edge_att = att_t.view(n_graphs, -1), att_s.view(n_graphs, -1)
+                x_t0 = ops.row_scale(x_t0, att_t)
+                x_s0 = ops.row_scale(x_s0, att_s)
+                dn = datas[k + 1]
+                x_t0 = cluster_mean(x_t0, pos_ts[k], dn.x_t.shape[0])
+                x_s0 = cluster_mean(x_s0, pos_ss[k], dn.x_s.shape[0])  # inf members dropped
+                adj_t = (dn.edge_index_t.to(dev), dn.edge_weight_t.to(dev))
+                adj_s = (dn.edge_index_s.to(dev), dn.edge_weight_s.to(dev))
+                k += 1
+                par_1 = adj2par1(dn.edge_index.to(dev), x_t0.shape[0], x_s0.shape[0])
+                D = degree(dn.edge_index.to(dev).view(-1), num_nodes=x_t0.shape[0]) + 1e-6
+        x_t, x_s = self.readout(x_t, adj_t, x_s, adj_s)
+        x = torch.cat([x_s.view(n_graphs, -1), x_t.view(n_graphs, -1)], dim=-1)
+        if x.size(1) != self.num_nodepedge:
+            raise ValueError(f"HL_HGAT_attpool: the last level has {x.size(1)} nodes + edges per "
+                             f"graph, the head was built with num_nodepedge={self.num_nodepedge}")
+        for i, _ in enumerate(self.mlp_channels):
+            x = self._mlp(getattr(self, "mlp%d" % i), x)
+        return ops.linear_blocks([x], self.out.weight, self.out.bias), x, node_att, edge_att

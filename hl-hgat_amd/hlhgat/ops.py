@@ -31,6 +31,7 @@ __all__ = [
     "mark_hodge", "spmm", "poly_basis", "hodge_poly_conv", "linear_blocks", "mlp2", "nei_value",
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
+    "temporal_conv", "leaky_maxpool_time", "time_readout",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -1588,6 +1589,200 @@ def att_score(Qc, Qs, Kr, w_cross: float, w_self: float, sqrt_dk: float,
         _req_dev(t, nm)
     return _AttScoreFn.apply(_rows2d(Qc, "Qc"), _rows2d(Qs, "Qs"), _rows2d(Kr, "K"),
                              float(w_cross), float(w_self), float(sqrt_dk), int(sigma))
+
+
+# ----------------------------------------------------------------------------
+# temporal front end (HL-HGAT-DEMO Inception1D): channels-last [N, T, C]
+# ----------------------------------------------------------------------------
+def _branch_arrays(weights):
+    couts = [int(w.size(0)) for w in weights]
+    tbs = [int(w.size(2)) for w in weights]
+    return couts, tbs, _arr(_lib.c_i64, couts), _arr(_lib.c_i32, tbs)
+
+
+def _tconv_pack(weights, cin: int, taps: int, flip: bool) -> torch.Tensor:
+    couts, _, c_couts, c_tbs = _branch_arrays(weights)
+    wp = torch.empty(taps * sum(couts) * cin, device=weights[0].device, dtype=torch.float32)
+    check(LIB.hlhgat_tconv_pack(len(weights), _arr(_lib.c_vp, [w.data_ptr() for w in weights]),
+                                c_couts, c_tbs, cin, taps, 1 if flip else 0, wp.data_ptr(),
+                                _stream(wp)), "tconv_pack")
+    return wp
+
+
+class _TemporalConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, nb, *params):
+        weights, biases = list(params[:nb]), list(params[nb:])
+        has_bias = biases[0] is not None
+        N, T, cin = x.shape
+        couts, tbs, _, _ = _branch_arrays(weights)
+        cout, taps = sum(couts), max(tbs)
+        y = torch.empty(N, T, cout, device=x.device, dtype=torch.float32)
+        if cin == 1 and nb == 1:
+            check(LIB.hlhgat_tconv_embed_fwd(x.data_ptr(), N, T, weights[0].data_ptr(),
+                                             _ptr(biases[0]), cout, taps, y.data_ptr(),
+                                             _stream(x)), "tconv_embed_fwd")
+        else:
+            wp = _tconv_pack(weights, cin, taps, False)
+            bias = None
+            if has_bias and nb == 1:
+                bias = biases[0]
+            elif has_bias:
+                bias = torch.empty(cout, device=x.device, dtype=torch.float32)
+                offs = [sum(couts[:b]) for b in range(nb)]
+                one = [1] * nb
+                check(LIB.hlhgat_copy2d_batched(
+                    nb, _arr(_lib.c_vp, [b.data_ptr() for b in biases]), _arr(_lib.c_i64, couts),
+                    _arr(_lib.c_vp, [bias.data_ptr() + 4 * o for o in offs]),
+                    _arr(_lib.c_i64, couts), _arr(_lib.c_i64, one), _arr(_lib.c_i64, couts),
+                    _stream(x)), "copy2d_batched")
+            # leading 1-tap / 3-tap branches: their column tiles skip the outer taps
+            n1 = n3 = 0
+            b = 0
+            while b < nb and tbs[b] == 1 and taps > 1:
+                n1 += couts[b]
+                b += 1
+            while b < nb and tbs[b] <= 3 and taps > 3:
+                n3 += couts[b]
+                b += 1
+            check(LIB.hlhgat_tconv_fwd(x.data_ptr(), N, T, cin, wp.data_ptr(), _ptr(bias), cout,
+                                       taps, n1, n3, y.data_ptr(), _stream(x)), "tconv_fwd")
+        ctx.nb, ctx.has_bias = nb, has_bias
+        ctx.save_for_backward(x, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, *weights = ctx.saved_tensors
+        nb = ctx.nb
+        N, T, cin = x.shape
+        couts, tbs, c_couts, c_tbs = _branch_arrays(weights)
+        cout, taps = sum(couts), max(tbs)
+        g = g.contiguous()
+        gx = None
+        if ctx.needs_input_grad[0]:
+            wt = _tconv_pack(weights, cin, taps, True)
+            gx = torch.empty(N, T, cin, device=x.device, dtype=torch.float32)
+            check(LIB.hlhgat_tconv_fwd(g.data_ptr(), N, T, cout, wt.data_ptr(), None, cin, taps,
+                                       0, 0, gx.data_ptr(), _stream(x)), "tconv_bwd_data")
+        gws = [None] * nb
+        gbs = [None] * nb
+        if any(ctx.needs_input_grad[2:]):
+            gws = [torch.empty_like(w) for w in weights]
+            gb = (torch.empty(cout, device=x.device, dtype=torch.float32)
+                  if ctx.has_bias else None)
+            wsf = LIB.hlhgat_tconv_bwd_weight_workspace_floats(N, T, cin, cout, taps)
+            ws = torch.empty(max(wsf, 1), device=x.device, dtype=torch.float32)
+            check(LIB.hlhgat_tconv_bwd_weight(
+                x.data_ptr(), g.data_ptr(), N, T, cin, cout, taps, nb,
+                _arr(_lib.c_vp, [w.data_ptr() for w in gws]), c_couts, c_tbs, _ptr(gb),
+                ws.data_ptr(), wsf, _stream(x)), "tconv_bwd_weight")
+            if gb is not None:
+                gbs = list(torch.split(gb, couts))
+        return (gx, None, *gws, *gbs)
+
+
+def temporal_conv(x: torch.Tensor, weights, biases=None) -> torch.Tensor:
+    """F.conv1d over time with zero padding taps/2 on channels-last series
+    x [N, T, Cin] -> [N, T, sum Cout_b]: the branches ``weights`` (nn.Conv1d
+    layout [Cout_b, Cin, taps_b], odd taps_b <= 5) read the same input and
+    their outputs are concatenated (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:
+    501-509) -- one implicit-GEMM launch on a weight packed on the device."""
+    if torch.is_tensor(weights):
+        weights = [weights]
+        biases = None if biases is None else [biases]
+    weights = list(weights)
+    nb = len(weights)
+    biases = [None] * nb if biases is None else list(biases)
+    _req_dev(x, "x")
+    if x.dim() != 3:
+        raise RuntimeError(f"hlhgat: temporal_conv x must be [N, T, C] (got {tuple(x.shape)})")
+    if len(biases) != nb or len({b is None for b in biases}) != 1:
+        raise RuntimeError("hlhgat: temporal_conv needs a bias for every branch or for none")
+    for w, b in zip(weights, biases):
+        _req_dev(w, "weight")
+        if w.dim() != 3 or w.size(1) != x.size(2):
+            raise RuntimeError(f"hlhgat: temporal_conv weight {tuple(w.shape)} for "
+                               f"{x.size(2)} input channels")
+        if b is not None:
+            _req_dev(b, "bias")
+    return _TemporalConvFn.apply(x.contiguous(), nb, *[w.contiguous() for w in weights],
+                                 *[None if b is None else b.contiguous() for b in biases])
+
+
+def maxpool_time_len(T: int, m: int) -> int:
+    """Output length of nn.MaxPool1d(m, stride=m-1, padding=(m-1)//2)."""
+    return int(LIB.hlhgat_maxpool_time_len(int(T), int(m)))
+
+
+class _LeakyMaxPoolTimeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, slope, m):
+        N, T, Cc = x.shape
+        To = maxpool_time_len(T, m)
+        y = torch.empty(N, To, Cc, device=x.device, dtype=torch.float32)
+        idx = torch.empty(N, To, Cc, device=x.device, dtype=torch.int32)
+        check(LIB.hlhgat_leaky_maxpool_time_fwd(x.data_ptr(), N, T, Cc, m, slope, y.data_ptr(),
+                                                idx.data_ptr(), _stream(x)),
+              "leaky_maxpool_time_fwd")
+        ctx.slope, ctx.m = slope, m
+        ctx.save_for_backward(x, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, idx = ctx.saved_tensors
+        N, T, Cc = x.shape
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        check(LIB.hlhgat_leaky_maxpool_time_bwd(x.data_ptr(), g.data_ptr(), idx.data_ptr(), N, T,
+                                                Cc, ctx.m, ctx.slope, gx.data_ptr(), _stream(x)),
+              "leaky_maxpool_time_bwd")
+        return gx, None, None
+
+
+def leaky_maxpool_time(x: torch.Tensor, slope: float, m: int) -> torch.Tensor:
+    """MaxPool1d(m, stride=m-1, padding=(m-1)//2)(LeakyReLU(slope)(x)) over the
+    time axis of x [N, T, C] -> [N, T', C] (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:
+    488, :505); the gradient goes to each window's first maximum."""
+    _req_dev(x, "x")
+    if x.dim() != 3:
+        raise RuntimeError(f"hlhgat: leaky_maxpool_time x must be [N, T, C] "
+                           f"(got {tuple(x.shape)})")
+    return _LeakyMaxPoolTimeFn.apply(x.contiguous(), float(slope), int(m))
+
+
+class _TimeReadoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, slope):
+        N, T, Cc = x.shape
+        y = torch.empty(N, 2 * Cc, device=x.device, dtype=torch.float32)
+        idx = torch.empty(N, Cc, device=x.device, dtype=torch.int32)
+        check(LIB.hlhgat_time_readout_fwd(x.data_ptr(), N, T, Cc, slope, y.data_ptr(),
+                                          idx.data_ptr(), _stream(x)), "time_readout_fwd")
+        ctx.slope = slope
+        ctx.save_for_backward(x, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, idx = ctx.saved_tensors
+        N, T, Cc = x.shape
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        check(LIB.hlhgat_time_readout_bwd(x.data_ptr(), g.data_ptr(), idx.data_ptr(), N, T, Cc,
+                                          ctx.slope, gx.data_ptr(), _stream(x)),
+              "time_readout_bwd")
+        return gx, None
+
+
+def time_readout(x: torch.Tensor, slope: float) -> torch.Tensor:
+    """[max_t | mean_t] of LeakyReLU(slope)(x) for x [N, T, C] -> [N, 2C]
+    (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:509-513)."""
+    _req_dev(x, "x")
+    if x.dim() != 3:
+        raise RuntimeError(f"hlhgat: time_readout x must be [N, T, C] (got {tuple(x.shape)})")
+    return _TimeReadoutFn.apply(x.contiguous(), float(slope))
 
 
 # ----------------------------------------------------------------------------

@@ -912,6 +912,74 @@ int hlhgat_prof_read(int kernel_class, int64_t* launches, double* total_ms,
 int hlhgat_graph_kernel_count(void* graph, const char* name_part, int64_t* kernels,
                               int64_t* matching);
 
+/* ---- temporal front end (Inception1D of the DEMO brain model) ----------- */
+/* Activations are channels-last: x [n, t, c] row-major, i.e. an [n*t, c]
+ * matrix whose rows the BatchNorm entries take unchanged.  taps is odd and at
+ * most 5; the zero padding of taps/2 applies per series at both ends. */
+
+/* Packs nb branch weights in nn.Conv1d layout w[b] [cout_b[b]][cin][taps_b[b]]
+ * (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:485-487, :490-492: kernel sizes 1, 3, 5
+ * on one input) into one weight of `taps` taps with structural zeros, the
+ * branches' output channels concatenated (the torch.cat of :505, :509):
+ * flip_transpose = 0: wp [taps][Cout][cin] for hlhgat_tconv_fwd;
+ * flip_transpose = 1: wp [taps][cin][Cout] with the taps reversed, the weight
+ * with which hlhgat_tconv_fwd(dy, cin := Cout, cout := cin) is the data
+ * gradient. */
+int hlhgat_tconv_pack(int nb, const float* const* w, const int64_t* cout_b,
+                      const int32_t* taps_b, int64_t cin, int taps, int flip_transpose,
+                      float* wp, void* stream);
+
+/* y[n][t][co] = bias[co] + sum_k sum_ci x[n][t + k - taps/2][ci] * wp[k][co][ci]
+ * (F.conv1d with padding taps/2 on the transposed layout, :502-504, :506-508):
+ * implicit GEMM on the fp32 MFMA.  bias may be NULL.  Output columns [0, n1)
+ * are declared to have only their centre tap non-zero and [n1, n1 + n3) only
+ * the centre three (the 1- and 3-tap branches of a packed weight): their
+ * 16-column tiles skip the other taps.  n1 = n3 = 0 for a dense weight. */
+int hlhgat_tconv_fwd(const float* x, int64_t n, int64_t t, int64_t cin, const float* wp,
+                     const float* bias, int64_t cout, int taps, int64_t n1, int64_t n3,
+                     float* y, void* stream);
+
+/* The embedding nn.Conv1d(1, c, taps, padding=taps/2) (:483, :501) on
+ * x [n, t] with w [c][1][taps]: y [n, t, c]. */
+int hlhgat_tconv_embed_fwd(const float* x, int64_t n, int64_t t, const float* w,
+                           const float* bias, int64_t c, int taps, float* y, void* stream);
+
+/* Scratch floats needed by hlhgat_tconv_bwd_weight. */
+int64_t hlhgat_tconv_bwd_weight_workspace_floats(int64_t n, int64_t t, int64_t cin,
+                                                 int64_t cout, int taps);
+
+/* Weight and bias gradient of hlhgat_tconv_fwd (the autograd of :502-508):
+ * dW[k][co][ci] = sum_{n,t} dy[n][t][co] * x[n][t + k - taps/2][ci], written
+ * to the nb branches' gradients dw[b] in their nn.Conv1d layout (see
+ * hlhgat_tconv_pack), and dbias[co] = sum dy (dbias [cout], may be NULL).
+ * Per-workgroup partial sums in `workspace`, reduced in a fixed order: no
+ * atomics, bitwise reproducible. */
+int hlhgat_tconv_bwd_weight(const float* x, const float* dy, int64_t n, int64_t t,
+                            int64_t cin, int64_t cout, int taps, int nb, float* const* dw,
+                            const int64_t* cout_b, const int32_t* taps_b, float* dbias,
+                            float* workspace, int64_t workspace_floats, void* stream);
+
+/* Output length of nn.MaxPool1d(m, stride=m-1, padding=(m-1)/2) (:488). */
+int64_t hlhgat_maxpool_time_len(int64_t t, int m);
+
+/* LeakyReLU(slope) then that max-pool over time (:505): y and idx
+ * [n, t', c], idx = the time step of the window's first maximum (the padding
+ * counts as -inf). */
+int hlhgat_leaky_maxpool_time_fwd(const float* x, int64_t n, int64_t t, int64_t c, int m,
+                                  float slope, float* y, int32_t* idx, void* stream);
+/* dx[n][t][c] = (x > 0 ? 1 : slope) * sum of dy over the windows whose
+ * maximum is step t (gather form, fixed order). */
+int hlhgat_leaky_maxpool_time_bwd(const float* x, const float* dy, const int32_t* idx,
+                                  int64_t n, int64_t t, int64_t c, int m, float slope,
+                                  float* dx, void* stream);
+
+/* LeakyReLU(slope) then [max_t | mean_t] (:509-513): y [n, 2c], idx [n, c] the
+ * step of the first maximum. */
+int hlhgat_time_readout_fwd(const float* x, int64_t n, int64_t t, int64_t c, float slope,
+                            float* y, int32_t* idx, void* stream);
+int hlhgat_time_readout_bwd(const float* x, const float* dy, const int32_t* idx, int64_t n,
+                            int64_t t, int64_t c, float slope, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

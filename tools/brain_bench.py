@@ -1,0 +1,258 @@
+"""Timings of the DEMO brain model's front end and head on the GPU.
+
+    python tools/brain_bench.py [--out profiles/brain_bench.json] [--reps 20]
+
+(a) Inception1D(64, 8, 3, if_readout=True) forward and forward+backward at
+    N = 1340 time courses (5 subjects x 268 regions) of T = 375 steps, and its
+    kernels one by one: the convolutions as a fraction of the 157.3 TF fp32
+    MFMA peak on their algorithmic flops (the non-zero taps of the three
+    branches), max-pool and readout as a fraction of the 8 TB/s HBM peak on
+    their algorithmic bytes.
+(b) one eager forward+backward of the checkpoint-shaped HL_HGAT_attpool on 5
+    copies of tests/golden/brain_skeleton.npz, coarse level from
+    hlhgat.hodge_dataset.mlgc_weighted.
+(c) last, in a child process with its own time limit: the same front end on
+    torch's conv1d / max_pool1d (MIOpen), for the ratio -- or the note that it
+    did not finish.
+
+Event timing after warm-up, median of --reps runs.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "hl-hgat_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+PEAK_TF, PEAK_GBS = 157.3, 8000.0
+N, T, C, NC, MP = 1340, 375, 64, 8, 3
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+class TorchInception1D(torch.nn.Module):
+    """The same computation on torch's own GPU ops (NCT layout)."""
+
+    def __init__(self):
+        super().__init__()
+        nn = torch.nn
+        self.embedding = nn.Conv1d(1, C, 5, padding=2)
+        self.s1 = nn.ModuleList([nn.Conv1d(C, C // 4, 1), nn.Conv1d(C, C // 2, 3, padding=1),
+                                 nn.Conv1d(C, C // 4, 5, padding=2)])
+        self.s2 = nn.ModuleList([nn.Conv1d(C, NC, 1), nn.Conv1d(C, 2 * NC, 3, padding=1),
+                                 nn.Conv1d(C, NC, 5, padding=2)])
+        self.bn1, self.bn2 = nn.BatchNorm1d(C), nn.BatchNorm1d(4 * NC)
+        self.pool = nn.MaxPool1d(MP, stride=MP - 1, padding=(MP - 1) // 2)
+
+    def forward(self, x):
+        F = torch.nn.functional
+        x = self.embedding(x.unsqueeze(1))
+        x = self.pool(F.leaky_relu(self.bn1(torch.cat([c(x) for c in self.s1], 1)), 0.1))
+        x = F.leaky_relu(self.bn2(torch.cat([c(x) for c in self.s2], 1)), 0.1)
+        return torch.cat([x.max(-1)[0], x.mean(-1)], -1)
+
+
+def front_end(mod, reps):
+    dev = torch.device("cuda:0")
+    mod = mod.to(dev).train()
+    x = torch.randn(N, T, device=dev)
+
+    def fwd():
+        with torch.no_grad():
+            return mod(x)
+
+    def fwd_bwd():
+        for p in mod.parameters():
+            p.grad = None
+        mod(x).sum().backward()
+
+    return {"fwd_ms": round(timed(fwd, reps), 4), "fwd_bwd_ms": round(timed(fwd_bwd, reps), 4)}
+
+
+def kernels(mod, reps):
+    """The front end's kernels one at a time, at the shapes of (a)."""
+    from hlhgat import ops
+    dev = torch.device("cuda:0")
+    rows = []
+
+    def conv(name, convs, t):
+        cin = convs[0].weight.size(1)
+        ws, bs = [c.weight for c in convs], [c.bias for c in convs]
+        x = torch.randn(N, t, cin, device=dev, requires_grad=True)
+        flops = 2.0 * N * t * cin * sum(w.size(0) * w.size(2) for w in ws)
+        with torch.no_grad():
+            f = timed(lambda: ops.temporal_conv(x, ws, bs), reps)
+        y = ops.temporal_conv(x, ws, bs)
+        g = torch.randn_like(y)
+
+        def bwd():
+            torch.autograd.grad(y, [x] + ws + bs, g, retain_graph=True)
+
+        b = timed(bwd, reps)
+        rows.append({"kernel": name + " fwd", "ms": round(f, 4), "gflop": round(flops / 1e9, 3),
+                     "frac_mfma_peak": round(flops / f / 1e9 / PEAK_TF, 4)})
+        rows.append({"kernel": name + " bwd (data + weight)", "ms": round(b, 4),
+                     "gflop": round(2 * flops / 1e9, 3),
+                     "frac_mfma_peak": round(2 * flops / b / 1e9 / PEAK_TF, 4)})
+
+    t2 = ops.maxpool_time_len(T, MP)
+    conv("embedding (VALU)", [mod.embedding], T)
+    conv("stage 1 conv", [mod.channel1_1, mod.channel2_1, mod.channel3_1], T)
+    conv("stage 2 conv", [mod.channel1_2, mod.channel2_2, mod.channel3_2], t2)
+
+    def mem(name, fn_f, x, out_bytes):
+        with torch.no_grad():
+            f = timed(lambda: fn_f(x), reps)
+        y = fn_f(x)
+        g = torch.randn_like(y)
+        b = timed(lambda: torch.autograd.grad(y, [x], g, retain_graph=True), reps)
+        by_f = 4.0 * x.numel() + out_bytes
+        by_b = 8.0 * x.numel() + out_bytes  # x, dy + idx, dx
+        rows.append({"kernel": name + " fwd", "ms": round(f, 4), "mbytes": round(by_f / 1e6, 2),
+                     "frac_hbm_peak": round(by_f / f / 1e6 / PEAK_GBS, 4)})
+        rows.append({"kernel": name + " bwd", "ms": round(b, 4), "mbytes": round(by_b / 1e6, 2),
+                     "frac_hbm_peak": round(by_b / b / 1e6 / PEAK_GBS, 4)})
+
+    x1 = torch.randn(N, T, C, device=dev, requires_grad=True)
+    mem("leaky max-pool", lambda x: ops.leaky_maxpool_time(x, 0.1, MP), x1, 8.0 * N * t2 * C)
+    x2 = torch.randn(N, t2, 4 * NC, device=dev, requires_grad=True)
+    mem("readout", lambda x: ops.time_readout(x, 0.1), x2, 12.0 * N * 4 * NC)
+    return rows
+
+
+class _Level:
+    pass
+
+
+def head(reps):
+    import hlhgat
+    from hlhgat.hodge_dataset import PairData, hodge_coo_from_boundary, mlgc_weighted
+    dev = torch.device("cuda:0")
+    g = np.load(os.path.join(REPO, "tests", "golden", "brain_skeleton.npz"))
+    n, B = int(g["n_nodes"]), 5
+    ei = torch.from_numpy(g["edge_index"].astype(np.int64))
+    E = ei.shape[1]
+    ei_t, w_t, ei_s, w_s = hodge_coo_from_boundary(g["edge_index"], n, float(g["lmax"]))
+    gen = torch.Generator().manual_seed(0)
+    fine = PairData(x_s=torch.randn(E, 1, generator=gen), edge_index_s=ei_s, edge_weight_s=w_s,
+                    x_t=torch.randn(n, T, generator=gen), edge_index_t=ei_t, edge_weight_t=w_t,
+                    edge_index=ei)
+    fine.num_node1, fine.num_edge1 = n, E
+    coarse, c_node, c_edge = mlgc_weighted(fine)
+    n1, E1 = int(coarse.num_node1), int(coarse.num_edge1)
+
+    def level(d, nn_, ne_, xt, xs):
+        lv = _Level()
+        lv.x_t = torch.cat([xt] * B).to(dev)
+        lv.x_s = torch.cat([xs] * B).to(dev)
+        for side, cnt in (("t", nn_), ("s", ne_)):
+            e = getattr(d, "edge_index_" + side)
+            setattr(lv, "edge_index_" + side, torch.cat([e + b * cnt for b in range(B)], 1).to(dev))
+            setattr(lv, "edge_weight_" + side,
+                    getattr(d, "edge_weight_" + side).repeat(B).to(dev))
+        lv.edge_index = torch.cat([torch.as_tensor(d.edge_index) + b * nn_ for b in range(B)],
+                                  1).to(dev)
+        lv.num_node1 = torch.full((B,), nn_, dtype=torch.int64)
+        lv.num_edge1 = torch.full((B,), ne_, dtype=torch.int64)
+        return lv
+
+    l0 = level(fine, n, E, fine.x_t, fine.x_s)
+    l1 = level(coarse, n1, E1, coarse.x_t, coarse.x_s)
+    l0.pos_t = c_node.view(-1).repeat(B).to(dev)
+    l0.pos_s = c_edge.view(-1).repeat(B).to(dev)
+    m = hlhgat.HL_HGAT_attpool(channels=[2, 2, 2], filters=[32, 64, 128], mlp_channels=[], K=4,
+                               pool_num=1, num_nodepedge=n1 + E1).to(dev).train()
+
+    def step():
+        for p in m.parameters():
+            p.grad = None
+        out = m([l0, l1], device=dev)[0]
+        out.sum().backward()
+
+    ms = timed(step, max(reps // 4, 5), warmup=2)
+    return {"graphs": B, "nodes": n, "edges": E, "coarse_nodes": n1, "coarse_edges": E1,
+            "nnz_L1": int(ei_s.shape[1]), "fwd_bwd_ms": round(ms, 3)}
+
+
+def torch_child(args, res):
+    """Last GPU step of the run: torch's own ops in a child with a time limit."""
+    t0 = time.time()
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-only", "--reps",
+                            str(args.reps)], capture_output=True, text=True,
+                           timeout=args.torch_timeout)
+        if r.returncode == 0:
+            tt = json.loads(r.stdout.strip().splitlines()[-1])
+            tt["ratio_fwd"] = round(tt["fwd_ms"] / res["inception1d_hip"]["fwd_ms"], 3)
+            tt["ratio_fwd_bwd"] = round(tt["fwd_bwd_ms"] / res["inception1d_hip"]["fwd_bwd_ms"], 3)
+            res["inception1d_torch_ops"] = tt
+        else:
+            res["inception1d_torch_ops"] = {"error": r.stderr.strip()[-400:]}
+    except subprocess.TimeoutExpired:
+        res["inception1d_torch_ops"] = {
+            "error": f"torch conv1d / max_pool1d did not finish in {args.torch_timeout} s "
+                     f"(waited {time.time() - t0:.0f} s)"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "brain_bench.json"))
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--torch-only", action="store_true")
+    ap.add_argument("--torch-timeout", type=int, default=150)
+    ap.add_argument("--skip-head", action="store_true")
+    ap.add_argument("--skip-torch", action="store_true",
+                    help="no torch-ops child (e.g. under a kernel trace)")
+    args = ap.parse_args()
+    if args.torch_only:
+        print(json.dumps(front_end(TorchInception1D(), args.reps)), flush=True)
+        return
+    import hlhgat
+    from hlhgat import _lib, ops
+    res = {"shape": {"N": N, "T": T, "in_channels": C, "num_channels": NC, "maxpool": MP},
+           "bn_rows": N * T,
+           "bn_workspace_bytes": int(_lib.LIB.hlhgat_bn_workspace_bytes(N * T, C))}
+    mod = hlhgat.Inception1D(C, NC, MP, if_readout=True)
+    res["inception1d_hip"] = front_end(mod, args.reps)
+    with torch.no_grad():
+        y = mod(torch.randn(N, T, device="cuda:0"))
+    res["bn_502500_rows_ok"] = bool(torch.isfinite(y).all())
+    ops.check_device_errors()
+    res["kernels"] = kernels(mod, args.reps)
+    if not args.skip_head:
+        res["head_5x_skeleton"] = head(args.reps)
+    ops.check_device_errors()
+    torch.cuda.synchronize()
+    if not args.skip_torch:
+        torch_child(args, res)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
