@@ -1891,8 +1891,59 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
 };
 
 // ---------------------------------------------------------------------------
+// Training-mode feature dropout (csrc/dropout.hip): y = keep ? x * s : 0 with
+// the Philox mask of (state = {seed, step} on the device, site, element); the
+// backward regenerates the mask from the forward's snapshot of the state, so
+// no mask is stored.  out: a [n, d] row-strided destination (DenseConcat sink).
+// ---------------------------------------------------------------------------
+class DropoutFn : public torch::autograd::Function<DropoutFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, Tensor x, int64_t T, double s, Tensor state,
+                        int64_t site, OptT out) {
+    req(x, "x");
+    Tensor xs = rows2d(x);
+    const int64_t n = xs.size(0), d = xs.size(1);
+    TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.numel() == 2 &&
+                    state.is_contiguous(), "hlhgat: dropout state must be two int64 on the device");
+    if (has(out))
+      TORCH_CHECK(out->dim() == 2 && out->size(0) == n && out->size(1) == d &&
+                      out->stride(1) == 1 && out->stride(0) >= d && out->device() == x.device() &&
+                      out->scalar_type() == at::kFloat,
+                  "hlhgat: dropout out must be a [", n, ", ", d, "] row-strided fp32 block");
+    Tensor y = has(out) ? *out : at::empty({n, d}, xs.options());
+    Tensor snap = at::empty({2}, state.options());
+    chk(hlhgat_dropout_fwd(xs.data_ptr<float>(), ld_of(xs), n, d, (uint32_t)T, (float)s,
+                           state.data_ptr<int64_t>(), (uint32_t)site, snap.data_ptr<int64_t>(),
+                           y.data_ptr<float>(), ld_of(y), stream_of(xs)),
+        "dropout_fwd");
+    ctx->saved_data["T"] = T;
+    ctx->saved_data["s"] = s;
+    ctx->saved_data["site"] = site;
+    ctx->save_for_backward({snap});
+    return y;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto sv = ctx->get_saved_variables();
+    Tensor g = rows2d(grads[0]);
+    const int64_t n = g.size(0), d = g.size(1);
+    Tensor gx = at::empty({n, d}, g.options());
+    chk(hlhgat_dropout_bwd(g.data_ptr<float>(), ld_of(g), n, d,
+                           (uint32_t)ctx->saved_data["T"].toInt(),
+                           (float)ctx->saved_data["s"].toDouble(), sv[0].data_ptr<int64_t>(),
+                           (uint32_t)ctx->saved_data["site"].toInt(), gx.data_ptr<float>(),
+                           ld_of(gx), stream_of(g)),
+        "dropout_bwd");
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+// ---------------------------------------------------------------------------
 // python entry points
 // ---------------------------------------------------------------------------
+Tensor hip_dropout(Tensor x, int64_t T, double s, Tensor state, int64_t site, OptT out) {
+  return DropoutFn::apply(x, T, s, state, site, out);
+}
+
 Tensor conv_bn(Tensor x, Tensor a_rowptr, Tensor a_col, OptT a_val, Tensor t_rowptr, Tensor t_col,
                OptT t_val, int64_t nnz, int64_t kind, std::vector<Tensor> W, OptT bias, OptT bn_w,
                OptT bn_b, OptT bn_rm, OptT bn_rv, OptT bn_nbt, double momentum, double eps,
@@ -2404,6 +2455,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reduce_flush", &reduce_flush);
   m.def("node_from_edges", &node_from_edges);
   m.def("edge_from_nodes", &edge_from_nodes);
+  m.def("dropout", &hip_dropout);
   m.def("version", []() { return hlhgat_version(); });
 }
 

@@ -18,7 +18,7 @@ from .hodge_cheb_conv import (HodgeLaguerreConv, HodgeLaguerreFastConv, Inceptio
 from .distributed import global_max
 from .hodge_dataset import adj2par1, degree
 from . import nn as _nn
-from .nn import Abs, BatchNorm, Sequential, run_mlp_stack
+from .nn import Abs, BatchNorm, Sequential, _hip_dropout, run_mlp_stack
 
 __all__ = ["HL_HGCNN_zinc_dense_int3_pyr", "HL_HGCNN_pepfunc_dense_int3_pyr",
            "HL_HGCNN_CIFAR10SP_dense_int3_pyr", "HL_HGCNN_zinc_dense_poolint3_pyr",
@@ -877,7 +877,9 @@ class HL_HGAT_attpool(nn.Module):
         lin, bn, act, drop = seq
         x = ops.batch_norm_act(ops.linear_blocks([x], lin.weight, lin.bias), bn, relu=False)
         x = act(x)
-        return x if (drop.p == 0.0 or not drop.training) else drop(x)
+        if drop.p == 0.0 or not drop.training:
+            return x
+        return ops.dropout(x, drop.p, True) if _hip_dropout(drop, x) else drop(x)
 
     def forward(self, datas, device="cuda:0"):
         n_pool = len(self.pool_loc)

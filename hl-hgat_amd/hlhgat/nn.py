@@ -147,6 +147,15 @@ class BCEWithLogitsLoss(tnn.BCEWithLogitsLoss):
         return super().forward(input, target)
 
 
+def _hip_dropout(m, x) -> bool:
+    """m is a live nn.Dropout that runs on the HIP path for the device tensor x
+    (ops.dropout); ops.HIP_DROPOUT = False leaves it to ATen."""
+    from . import ops
+    return (isinstance(m, tnn.Dropout) and m.p > 0.0 and m.training and not m.inplace
+            and ops.HIP_DROPOUT and torch.is_tensor(x) and x.is_cuda
+            and x.dtype == torch.float32)
+
+
 def _names(s: str) -> List[str]:
     return [t.strip() for t in s.split(",") if t.strip()]
 
@@ -220,8 +229,37 @@ class Sequential(tnn.Module):
                     return s
         return None
 
+    def _move_sink(self, i, k, pend) -> None:
+        """Entry i is a conv (with the k - 1 entries fused into it) that holds
+        a one-shot DenseConcat sink (_hlhgat_out).  When a live Dropout follows
+        on the same variable -- directly or after one activation (the
+        LeakyReLU blocks) -- the sink moves to the Dropout: the conv writes a
+        fresh tensor (the y its fused ReLU saved is never overwritten) and the
+        Dropout writes the dropped values straight into the slab column block,
+        so DenseConcat.append finds them in place."""
+        from . import ops
+        conv = getattr(self, f"module_{i}")
+        sink = getattr(conv, "_hlhgat_out", None)
+        r0 = self._routes[i]
+        if sink is None or not ops.HIP_DROPOUT or len(r0[1]) != 1:
+            return
+        var = r0[1]
+
+        def on_var(j):
+            return j < self._n and self._routes[j][0] == var and self._routes[j][1] == var
+
+        j = i + k
+        if (on_var(j) and self._fuse[j] is None
+                and isinstance(getattr(self, f"module_{j}"), (tnn.ReLU, tnn.LeakyReLU))):
+            j += 1
+        if on_var(j) and self._fuse[j] is None and _hip_dropout(getattr(self, f"module_{j}"),
+                                                                sink):
+            conv._hlhgat_out = None
+            pend[var[0]] = sink
+
     def _run(self, env, lo, hi):
         out = None
+        pend = {}  # variable -> DenseConcat sink moved from its conv to its live Dropout
         i = lo
         while i < hi:
             ins, outs = self._routes[i]
@@ -230,7 +268,12 @@ class Sequential(tnn.Module):
             if fuse is None:
                 if isinstance(fn, tnn.Dropout) and (fn.p == 0.0 or not fn.training):
                     out = env[ins[0]]  # identity: no copy kernel
+                elif _hip_dropout(fn, env[ins[0]]):
+                    from .ops import dropout
+                    out = dropout(env[ins[0]], fn.p, True, out=pend.pop(ins[0], None))
                 else:
+                    if hasattr(fn, "forward_bn"):
+                        self._move_sink(i, 1, pend)
                     out = fn(*[env[n] for n in ins])
                     if isinstance(fn, tnn.ReLU):
                         tap(fn, out)
@@ -242,6 +285,7 @@ class Sequential(tnn.Module):
                 i += 2
             else:
                 bn = getattr(self, f"module_{i + 1}").module
+                self._move_sink(i, fuse[1], pend)
                 out = fn.forward_bn(*[env[n] for n in ins], bn=bn,
                                     relu=fuse[0] == "conv_bn_relu")
                 if fuse[0] == "conv_bn_relu":
@@ -299,7 +343,7 @@ def run_sequential(seq: tnn.Sequential, blocks) -> torch.Tensor:
     concatenation is its input, e.g. cat[x_s2t, x_t] of NodeEdgeInt,
     lib/Hodge_Cheb_Conv.py:307-308) without materialising the cat, and each
     BatchNorm1d followed by ReLU runs as one fused op."""
-    from .ops import batch_norm_act, linear_blocks
+    from .ops import batch_norm_act, dropout, linear_blocks
     mods = list(seq)
     h = None
     i = 0
@@ -315,6 +359,8 @@ def run_sequential(seq: tnn.Sequential, blocks) -> torch.Tensor:
             i += relu
         elif isinstance(m, tnn.Dropout) and (m.p == 0.0 or not m.training):
             pass
+        elif h is not None and _hip_dropout(m, h):
+            h = dropout(h, m.p, True)
         else:
             h = m(h if h is not None else torch.cat(list(blocks), -1))
             if isinstance(m, tnn.ReLU):

@@ -31,7 +31,7 @@ __all__ = [
     "mark_hodge", "spmm", "poly_basis", "hodge_poly_conv", "linear_blocks", "mlp2", "nei_value",
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
-    "temporal_conv", "leaky_maxpool_time", "time_readout",
+    "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -1579,6 +1579,138 @@ def row_scale(x: torch.Tensor, a: torch.Tensor, out: Optional[torch.Tensor] = No
     if gsink is not None and (gsink[0] is None or gsink[0].shape != x.shape):
         gsink = None
     return _RowScaleFn.apply(x, a, out, gsink)
+
+
+# ----------------------------------------------------------------------------
+# Training-mode feature dropout (counter-based Philox mask, csrc/dropout.hip)
+# ----------------------------------------------------------------------------
+HIP_DROPOUT = True  # A/B hook: False = a live nn.Dropout runs ATen's dropout
+
+_MASK64 = (1 << 64) - 1
+
+
+def dropout_rank_seed(seed: int, rank: int) -> int:
+    """The seed of data-parallel rank `rank`: (seed + rank * 0x9E3779B97F4A7C15)
+    mod 2^64, so the ranks of one job draw different masks (pure host)."""
+    return (int(seed) + int(rank) * 0x9E3779B97F4A7C15) & _MASK64
+
+
+class _DropoutState:
+    """Per-device dropout state: {seed, step} as two int64 ON the device (the
+    kernels read them, so a captured step sees the advance) and the host-side
+    call counter `site` baked into each launch."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.rank = 0
+        self.site = 0
+        self.dev = torch.empty(2, dtype=torch.int64, device=device)
+        self.set(torch.initial_seed())
+
+    def set(self, seed: int) -> None:
+        s = dropout_rank_seed(seed, self.rank)
+        s = s - (1 << 64) if s >= (1 << 63) else s  # the same 64 bits as int64
+        self.dev.copy_(torch.tensor([s, 0], dtype=torch.int64))
+        self.site = 0
+
+    def next_site(self) -> int:
+        s = self.site
+        self.site = (s + 1) & 0xffffffff
+        return s
+
+
+_DROPOUT_STATES = {}
+
+
+def _dropout_device(device) -> torch.device:
+    d = torch.device("cuda" if device is None else device)
+    if d.type != "cuda":
+        raise RuntimeError(f"hlhgat: dropout state lives on a ROCm device (got {d})")
+    return torch.device("cuda", torch.cuda.current_device() if d.index is None else d.index)
+
+
+def _dropout_st(device) -> _DropoutState:
+    d = _dropout_device(device)
+    st = _DROPOUT_STATES.get(d.index)
+    if st is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("hlhgat: the dropout state of a device must exist before a graph "
+                               "capture (call ops.dropout_state / dropout_manual_seed first)")
+        st = _DROPOUT_STATES[d.index] = _DropoutState(d)
+    return st
+
+
+def dropout_manual_seed(seed: int, device=None) -> None:
+    """seed := seed (offset by the rank set with dropout_set_rank), step := 0,
+    site := 0 on `device` (default: the current ROCm device)."""
+    _dropout_st(device).set(int(seed) & _MASK64)
+
+
+def dropout_set_rank(rank: int, device=None) -> None:
+    """Data-parallel rank of this process (TrainStep, world > 1): the current
+    and every later seed of `device` is offset by dropout_rank_seed."""
+    st = _dropout_st(device)
+    if rank != st.rank:
+        seed = (dropout_state(device)[0] - st.rank * 0x9E3779B97F4A7C15) & _MASK64
+        st.rank = int(rank)
+        st.set(seed)
+
+
+def dropout_advance(device=None) -> None:
+    """step += 1 on the device (one launch on the current stream; captured into
+    a graph it advances on every replay): the next step's masks."""
+    st = _dropout_st(device)
+    check(LIB.hlhgat_dropout_advance(st.dev.data_ptr(),
+                                     torch._C._cuda_getCurrentRawStream(st.device.index)),
+          "dropout_advance")
+
+
+def dropout_state(device=None) -> Tuple[int, int, int]:
+    """(seed, step, site) of `device` -- seed as an unsigned 64-bit value.
+    Synchronises (tests, checkpoints)."""
+    st = _dropout_st(device)
+    seed, step = st.dev.tolist()
+    return seed & _MASK64, step, st.site
+
+
+def dropout_params(p: float) -> Tuple[int, float]:
+    """(T, s) of the mask rule: keep iff (word >> 8) >= T = floor(p * 2^24);
+    s = float32(1 / (1 - p)) rounded once from double (0 at p = 1: all dropped)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    T = int(math.floor(p * 16777216.0))
+    s = 0.0 if p == 1.0 else 1.0 / (1.0 - p)
+    return T, s
+
+
+def dropout(x: torch.Tensor, p: float, training: bool = True,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.nn.functional.dropout(x, p, training) for the Dropout that ends
+    every HL block (lib/Hodge_ST_Model.py:556-566) as one HIP pass each way:
+    the mask is a function of (seed, step, site, element) (csrc/dropout.hip),
+    regenerated in the backward instead of stored, and drawn afresh by every
+    replay of a captured step (dropout_advance).  Masks are not ATen's: parity
+    with the reference under dropout is distributional.  p == 0 or eval
+    returns x itself (no launch, no site); CPU tensors go to torch.  out: a
+    [n, d] row-strided destination (DenseConcat.sink) for y.  Each launch
+    takes the device's next `site`."""
+    if p == 0.0 or not training:
+        return x
+    if not x.is_cuda:
+        return torch.nn.functional.dropout(x, p, training)
+    _req_dev(x, "x")
+    T, s = dropout_params(p)
+    shape = x.shape
+    x2 = _rows2d(x if x.dim() == 2 else x.reshape(-1, shape[-1] if x.dim() else 1), "x")
+    if out is not None and (x.dim() != 2 or tuple(out.shape) != tuple(x2.shape)
+                            or out.stride(1) != 1 or out.stride(0) < out.size(1)):
+        raise RuntimeError(f"hlhgat: dropout out {tuple(out.shape)} vs x {tuple(x.shape)}")
+    if x2.numel() == 0:
+        return x if out is None else out
+    st = _dropout_st(x.device)
+    y = _ext.dropout(x2, T, s, st.dev, st.next_site(), out)  # C++ autograd node
+    return y if x.dim() == 2 else y.view(shape)
 
 
 def att_score(Qc, Qs, Kr, w_cross: float, w_self: float, sqrt_dk: float,

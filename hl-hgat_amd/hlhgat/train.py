@@ -354,6 +354,18 @@ class TrainStep:
             # cannot be captured: this step runs eagerly (RCCL ones can)
             self.graphs = False
             self.graphs_off = "forward collectives under a host (gloo) backend"
+        # feature dropout on the HIP path (ops.dropout): the device-side step
+        # of its mask counter advances once per step (_prepare); its state is
+        # made here, outside any capture, and offset per rank so that the
+        # ranks of a data-parallel job draw different masks
+        self._dropouts = [m for m in model.modules()
+                          if isinstance(m, torch.nn.Dropout) and m.p > 0.0] \
+            if dev.type == "cuda" else []
+        if self._dropouts:
+            if self.world > 1:
+                ops.dropout_set_rank(dist.get_rank(), dev)
+            else:
+                ops.dropout_state(dev)
         self.max_graphs = max_graphs
         self._graphs: Dict[Tuple, _Captured] = {}
         self._pool = None
@@ -367,7 +379,11 @@ class TrainStep:
     def _prepare(self) -> bool:
         """Start of a step: zero the gradient bucket.  With the HIP Adam the
         step count is incremented in the same launch (hlhgat_adam_prepare);
-        returns whether it was (the update then must not count again)."""
+        returns whether it was (the update then must not count again).  A
+        model with a live Dropout also advances the dropout step here (one
+        more launch; captured, it draws fresh masks on every replay)."""
+        if self._dropouts and ops.HIP_DROPOUT and any(m.training for m in self._dropouts):
+            ops.dropout_advance(self.device)
         if self._hip_adam:
             ops.adam_prepare(self.flat_grad, self.opt.state[self.master]["step"])
             return True

@@ -980,6 +980,31 @@ int hlhgat_time_readout_fwd(const float* x, int64_t n, int64_t t, int64_t c, flo
 int hlhgat_time_readout_bwd(const float* x, const float* dy, const int32_t* idx, int64_t n,
                             int64_t t, int64_t c, float slope, float* dx, void* stream);
 
+/* ---- training-mode feature dropout -------------------------------------- */
+/* Dropout(p=dropout_ratio), the tail of every HL block (lib/Hodge_ST_Model.py:
+ * 556-566; 0.25 in the CIFAR10SP, peptides-func and TSP training scripts),
+ * with a counter-based mask instead of a stored one.  Element e = row * d + col
+ * (a logical index, independent of ldx / ldy) takes word (e & 3) of
+ *   philox4x32-10(counter {g lo, g hi, site, step lo}, key {seed lo, seed hi}),
+ *   g = e >> 2,
+ * and is kept iff (word >> 8) >= T, T = floor(p * 2^24) <= 2^24:
+ *   y = keep ? x * s : 0,  s = float(1 / (1 - p)).
+ * state = {seed, step}, two int64 in device memory read by the kernel (a
+ * captured launch sees the step advanced between replays); site is the
+ * caller's call counter.  The forward copies the {seed, step} it used to
+ * snap (two int64, device); x / y are [n, d] with leading dimensions ldx /
+ * ldy (y may be a column block of a wider slab).  n * d == 0 is a no-op. */
+int hlhgat_dropout_fwd(const float* x, int64_t ldx, int64_t n, int64_t d, uint32_t T, float s,
+                       const int64_t* state, uint32_t site, int64_t* snap, float* y,
+                       int64_t ldy, void* stream);
+/* dx = keep ? dy * s : 0 with the mask regenerated from the forward's snap
+ * (no mask is stored); dy may be a column block of a gradient slab. */
+int hlhgat_dropout_bwd(const float* dy, int64_t lddy, int64_t n, int64_t d, uint32_t T, float s,
+                       const int64_t* snap, uint32_t site, float* dx, int64_t lddx,
+                       void* stream);
+/* state[1] += 1 (one thread): the next step's masks.  Capturable. */
+int hlhgat_dropout_advance(int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@ configs 3 and 4 on one GPU, eager (no hipGraph: the two MLGC levels change
 shape every batch).
 
     python tools/heads_bench.py [--configs cifar peptides] [--steps 10]
+                                [--dropout-ratio 0.25 [--ab-rounds 5]]
 
 cifar    (config 3): HL_HGCNN_CIFAR10SP_dense_int3_attpool(channels=[2,2,2],
          filters=[64,128,256], mlp=[256], K=4, keig=10, pool_loc=1, l=0.5),
@@ -56,10 +57,12 @@ def make_batch(kind, graphs, seed):
     return two_level_batch(kind, graphs, seed=seed)
 
 
-def run(name, steps, warmup, n_batches, dev):
+def run(name, steps, warmup, n_batches, dev, dropout_ratio=0.0, ab_rounds=0):
     import hlhgat
     from hlhgat import ops
     c = CONFIGS[name]
+    if dropout_ratio:
+        c = dict(c, kw=dict(c["kw"], dropout_ratio=dropout_ratio))
     t0 = time.time()
     batches = []
     for s in range(n_batches):
@@ -90,17 +93,40 @@ def run(name, steps, warmup, n_batches, dev):
         m.zero_grad(set_to_none=True)
         loss.backward()
 
+    def window():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(steps):
+            step(i)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps
+
+    ab = {}
+    if ab_rounds:
+        # A/B of ops.HIP_DROPOUT in one process, windows interleaved (off, on,
+        # off, on, ...); off = ATen's dropout, the behaviour before ops.dropout
+        for flag in (False, True):
+            ops.HIP_DROPOUT = flag
+            for i in range(warmup):
+                step(i)
+        ms = {False: [], True: []}
+        for _ in range(ab_rounds):
+            for flag in (False, True):
+                ops.HIP_DROPOUT = flag
+                ms[flag].append(round(window() * 1e3, 3))
+        ops.HIP_DROPOUT = True
+        med = {f: sorted(v)[len(v) // 2] for f, v in ms.items()}
+        ab = {"ms_aten_dropout": ms[False], "ms_hip_dropout": ms[True],
+              "median_ms_aten_dropout": med[False], "median_ms_hip_dropout": med[True],
+              "spread_aten_dropout": round((max(ms[False]) - min(ms[False])) / med[False], 4),
+              "hip_over_aten": round(med[True] / med[False], 4)}
     for i in range(warmup):
         step(i)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        step(i)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
+    dt = window()
     b0 = batches[0] if c["kind"] == "tsp" else batches[0][0]
     op = ops.hodge_operator(b0.edge_index_s, b0.edge_weight_s, b0.x_s.shape[0])
-    return {"config": name, "head": c["cls"], "graphs_per_step": c["graphs"],
+    extra = {"dropout_ratio": dropout_ratio, **ab} if dropout_ratio else {}
+    return {**extra, "config": name, "head": c["cls"], "graphs_per_step": c["graphs"],
             "value": round(c["graphs"] / dt, 1), "unit": "graphs/s", "ms_per_step": round(dt * 1e3, 3),
             "mode": "eager fwd+loss+bwd", "params": n_params, "rows_t": int(b0.x_t.shape[0]),
             "rows_s": int(b0.x_s.shape[0]), "nnz_s": int(b0.edge_index_s.shape[1]),
@@ -113,10 +139,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches", type=int, default=2)
+    ap.add_argument("--dropout-ratio", type=float, default=0.0,
+                    help="dropout_ratio of the head (the reference scripts train configs 3-5 "
+                         "with 0.25); 0 = the runs as they always were")
+    ap.add_argument("--ab-rounds", type=int, default=0,
+                    help="with --dropout-ratio: this many interleaved (ATen, HIP) windows of "
+                         "--steps steps each, reported per window")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for name in args.configs:
-        print(json.dumps(run(name, args.steps, args.warmup, args.batches, dev)), flush=True)
+        print(json.dumps(run(name, args.steps, args.warmup, args.batches, dev,
+                             args.dropout_ratio, args.ab_rounds if args.dropout_ratio else 0)),
+              flush=True)
 
 
 if __name__ == "__main__":

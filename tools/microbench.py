@@ -41,10 +41,83 @@ def timeit(fn, reps=50, warm=5):
     return ts[len(ts) // 2], ts[0]
 
 
+# [n, d] of the HL block outputs a live Dropout sees: config 2 (ZINC, 1000
+# graphs), config 3 (CIFAR10SP, 256 graphs: nodes / edges at level 0) and
+# config 5 (TSP, 4 graphs of 10k nodes)
+DROPOUT_SHAPES = [("cfg2 nodes", 23259, 64), ("cfg2 edges", 24927, 64),
+                  ("cfg3 nodes", 30208, 64), ("cfg3 edges", 143192, 64),
+                  ("cfg5 nodes", 40000, 32), ("cfg5 edges", 206858, 32),
+                  ("cfg5 edges", 206858, 128)]
+
+
+def replayed(launch, reps, k=20):
+    """us per launch with k launches captured into one hipGraph and replayed:
+    the kernels back to back, without the host's per-call enqueue time.
+    `launch` issues C-ABI launches only (no autograd, no allocation: an
+    autograd backward inside a capture runs on the stream of its forward,
+    which for a forward made before the capture is not the capturing stream)."""
+    launch()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(k):
+            launch()
+    us, mn = timeit(g.replay, reps)
+    return us / k, mn / k
+
+
+def dropout_leg(rec, reps, dev):
+    """Dropout forward and backward at p = 0.25, contiguous and into / out of
+    a column block of a 4d-wide slab.  "replayed": the kernels alone (20
+    hlhgat_dropout_fwd / _bwd launches captured and replayed); "eager call":
+    one ops.dropout / autograd call with its host enqueue, ATen's beside it.
+    GB/s against the 8 n d algorithmic bytes of one pass (read x, write y)."""
+    from hlhgat import ops
+    from hlhgat._lib import LIB, check
+    F = torch.nn.functional
+    ops.dropout_manual_seed(1)
+    T, s = ops.dropout_params(0.25)
+    state = ops._dropout_st(dev).dev
+    snap = torch.zeros(2, dtype=torch.int64, device=dev)
+    for tag, n, d in DROPOUT_SHAPES:
+        by = 8.0 * n * d
+        x = torch.randn(n, d, device=dev, requires_grad=True)
+        xd = x.detach()
+        g = torch.randn(n, d, device=dev)
+        out = torch.empty(n, d, device=dev)
+        slab = torch.randn(n, 4 * d, device=dev)
+        col = slab[:, d:2 * d]
+
+        def fwd(dst):
+            check(LIB.hlhgat_dropout_fwd(xd.data_ptr(), d, n, d, T, s, state.data_ptr(), 0,
+                                         snap.data_ptr(), dst.data_ptr(), dst.stride(0),
+                                         ops._stream(xd)), "dropout_fwd")
+
+        def bwd(src):
+            check(LIB.hlhgat_dropout_bwd(src.data_ptr(), src.stride(0), n, d, T, s,
+                                         snap.data_ptr(), 0, out.data_ptr(), d,
+                                         ops._stream(xd)), "dropout_bwd")
+
+        for name, launch in (("fwd", lambda: fwd(out)), ("fwd into slab", lambda: fwd(col)),
+                             ("bwd", lambda: bwd(g)), ("bwd from slab", lambda: bwd(col))):
+            us, mn = replayed(launch, reps)
+            rec(f"dropout_{name} hip {tag} [{n},{d}] replayed x20", us, mn, by)
+        y = ops.dropout(x, 0.25)
+        yt = F.dropout(x, 0.25, True)
+        for name, fn in (("fwd hip", lambda: ops.dropout(xd, 0.25)),
+                         ("bwd hip", lambda: torch.autograd.grad(y, x, g, retain_graph=True)),
+                         ("fwd torch", lambda: F.dropout(xd, 0.25, True)),
+                         ("bwd torch", lambda: torch.autograd.grad(yt, x, g, retain_graph=True))):
+            us, mn = timeit(fn, reps)
+            rec(f"dropout_{name} {tag} [{n},{d}] eager call", us, mn, by)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "microbench.json"))
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--only", choices=("dropout",), default=None,
+                    help="run this leg alone (default: every leg)")
     args = ap.parse_args()
     from hlhgat import ops
     from hlhgat.hodge_dataset import collate
@@ -64,6 +137,16 @@ def main():
         r.update(kw)
         res.append(r)
         print(json.dumps(r), flush=True)
+
+    def save():
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+    if args.only == "dropout":
+        dropout_leg(rec, args.reps, dev)
+        save()
+        return
 
     # ---- operators ------------------------------------------------------
     zb = zinc_like_batch(1000, seed=1).to(dev)
@@ -159,9 +242,9 @@ def main():
                                           5.656854, ops.SIGMA_SIGMOID), args.reps)
     rec("att_score n=24927 dk=32", us, mn, 4.0 * 24927 * 97)
 
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
+    # ---- dropout ----------------------------------------------------------
+    dropout_leg(rec, args.reps, dev)
+    save()
 
 
 if __name__ == "__main__":
