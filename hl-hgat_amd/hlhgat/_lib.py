@@ -150,6 +150,15 @@ SIGNATURES = {
     "hlhgat_bce_logits_bwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_l1_loss_fwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hlhgat_l1_loss_bwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "hlhgat_loss_workspace_bytes": (c_sz, [c_i64]),
+    "hlhgat_bce_reduce_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_f32,
+                                      c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "hlhgat_bce_reduce_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_f32,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hlhgat_cross_entropy_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp,
+                                         c_sz, c_vp, c_vp, c_vp]),
+    "hlhgat_cross_entropy_bwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp,
+                                         c_vp, c_vp, c_i64, c_vp]),
     "hlhgat_bn_sums_len": (c_i64, [c_i64]),
     "hlhgat_bn_sums_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
                                    c_i64, c_vp]),
@@ -195,6 +204,10 @@ POLY_LAGUERRE, POLY_CHEB, POLY_LAGUERRE_DEMO = 0, 1, 2
 SIGMA_SIGMOID, SIGMA_RELU = 0, 1
 DEVERR_BN_STATE = 1
 DEVERR_HODGE_SIZE = 2
+DEVERR_LABEL = 4
+LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
+CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
+LOSS_ONE_LAUNCH_MAX = 16384  # up to here the loss forwards need no workspace
 BN_LOG_MAX = 64
 PROF_POLY, PROF_PROJ, PROF_HODGE_NODE, PROF_HODGE_EDGE = 0, 1, 2, 3
 PROF_PROJ_BWD, PROF_BN_FWD, PROF_BN_BWD, PROF_PROJ_BN = 4, 5, 6, 7

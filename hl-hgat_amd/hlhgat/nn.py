@@ -16,8 +16,8 @@ from typing import Callable, List, Sequence, Tuple, Union
 import torch
 import torch.nn as tnn
 
-__all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "BCEWithLogitsLoss", "glorot",
-           "global_mean_pool"]
+__all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "BCEWithLogitsLoss", "FocalLoss",
+           "MaskedBCEWithLogitsLoss", "CrossEntropyLoss", "glorot", "global_mean_pool"]
 
 
 def glorot(t: torch.Tensor) -> None:
@@ -144,6 +144,117 @@ class BCEWithLogitsLoss(tnn.BCEWithLogitsLoss):
                 and not target.requires_grad and 0 < input.numel() <= self.FUSED_MAX):
             from . import ops
             return ops.bce_with_logits(input, target, self.reduction)
+        return super().forward(input, target)
+
+
+def _selection(target: torch.Tensor, mask, ignore_nan: bool):
+    """The boolean selection of the masked losses, or None for everything."""
+    m = None if mask is None else mask.bool()
+    if ignore_nan:
+        keep = ~torch.isnan(target)
+        m = keep if m is None else m & keep
+    return m
+
+
+def _hip_bce(input, target, mask) -> bool:
+    """input / target (/ mask) run on ops.bce_logits_loss."""
+    return (input.is_cuda and input.dtype == torch.float32 and input.shape == target.shape
+            and target.is_cuda and not target.requires_grad and input.numel() > 0
+            and (mask is None or (mask.shape == input.shape and mask.is_cuda
+                                  and not mask.requires_grad)))
+
+
+class MaskedBCEWithLogitsLoss(tnn.Module):
+    """BCE with logits over a selection of the elements,
+
+        m = mask.bool() & ~isnan(target)       (ignore_nan=True adds the second half)
+        F.binary_cross_entropy_with_logits(input[m], target[m], reduction=reduction)
+
+    with the selection made on the device inside the reduction
+    (ops.bce_logits_loss): static shapes, so ``criterion(out, y, mask=mask)``
+    captures in hlhgat.train.TrainStep where ``criterion(out[mask], y[mask])``
+    (a data-dependent gather) cannot.  Every size runs on HIP, in a fixed
+    summation order.  An empty selection gives loss 0 and a zero gradient on
+    the HIP path (torch: NaN).  CPU tensors, non-fp32 input and
+    reduction="none" go to the torch expression above."""
+
+    def __init__(self, reduction: str = "mean", ignore_nan: bool = False):
+        super().__init__()
+        self.reduction = reduction
+        self.ignore_nan = ignore_nan
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor, mask=None) -> torch.Tensor:
+        if self.reduction in ("mean", "sum") and _hip_bce(input, target, mask):
+            from . import ops
+            return ops.bce_logits_loss(input, target, mask, ignore_nan=self.ignore_nan,
+                                       reduction=self.reduction)
+        m = _selection(target, mask, self.ignore_nan)
+        if m is not None:
+            input, target = input[m], target[m]
+        return tnn.functional.binary_cross_entropy_with_logits(input, target,
+                                                               reduction=self.reduction)
+
+
+class FocalLoss(tnn.Module):
+    """The reference's FocalLoss (lib/Loss_function.py:14-26; the peptides-func
+    and TSP objective, main_pepfunc...:179-186, main_TSP...:321), a scalar
+    function of the MEAN BCE b:  loss = scale * alpha * (1 - exp(-b))**gamma * b
+    with the reference's constructor defaults and scale = 1e4.
+
+    ``criterion(out[mask], y[mask])`` works as in the reference (eager).  The
+    capture-safe forms are ``criterion(out, y, mask=mask)`` and
+    ``FocalLoss(ignore_nan=True)(out, y)`` (mask = ~isnan(y), taken on the
+    device): static shapes, one fixed-order HIP reduction at every size
+    (ops.bce_logits_loss).  An empty selection gives loss 0 and a zero
+    gradient on the HIP path (torch: NaN).  CPU tensors, non-fp32 input, class
+    weights and 0 < gamma < 1 go to the reference's torch expression, which on
+    CPU reproduces the reference class exactly."""
+
+    def __init__(self, alpha=0.25, gamma=2, weight=None, scale=1e4, ignore_nan=False):
+        super().__init__()
+        self.alpha = alpha
+        self.gamma = gamma
+        self.weight = weight
+        self.scale = scale
+        self.ignore_nan = ignore_nan
+        self.bce_fn = tnn.BCEWithLogitsLoss(weight=self.weight)
+
+    def forward(self, preds: torch.Tensor, labels: torch.Tensor, mask=None) -> torch.Tensor:
+        if (self.weight is None and (self.gamma == 0 or self.gamma >= 1)
+                and _hip_bce(preds, labels, mask)):
+            from . import ops
+            return ops.bce_logits_loss(preds, labels, mask, ignore_nan=self.ignore_nan,
+                                       focal=(self.alpha, self.gamma, self.scale))
+        m = _selection(labels, mask, self.ignore_nan)
+        if m is not None:
+            preds, labels = preds[m], labels[m]
+        logpt = -self.bce_fn(preds, labels)
+        pt = torch.exp(logpt)
+        loss = -((1 - pt) ** self.gamma) * self.alpha * logpt
+        return loss * self.scale
+
+
+class CrossEntropyLoss(tnn.CrossEntropyLoss):
+    """torch.nn.CrossEntropyLoss (the CIFAR10SP training loss,
+    main_cifar10SP...:137,203; torch's constructor, e.g.
+    ``CrossEntropyLoss(ignore_index=-100, reduction="mean")``) whose "mean" /
+    "sum" reductions over fp32 logits [R, C <= 64] and class-index targets on
+    ROCm run on HIP (ops.cross_entropy: fixed summation order; all rows
+    ignored gives 0, not NaN; a label outside [0, C) raises the device error
+    word instead of a device assert).  Class weights, label smoothing,
+    class-probability targets, C > 64, "none", other shapes and CPU tensors
+    go to torch."""
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if (self.weight is None and self.label_smoothing == 0.0
+                and self.reduction in ("mean", "sum") and input.is_cuda
+                and input.dtype == torch.float32 and input.dim() == 2 and target.dim() == 1
+                and target.is_cuda and not target.is_floating_point()
+                and target.size(0) == input.size(0) and input.size(0) > 0):
+            from . import _lib, ops
+            if 1 <= input.size(1) <= _lib.CE_MAX_CLASSES:
+                return ops.cross_entropy(input, target, ignore_index=self.ignore_index,
+                                         reduction=self.reduction)
         return super().forward(input, target)
 
 

@@ -32,6 +32,7 @@ __all__ = [
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
+    "bce_logits_loss", "cross_entropy",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -2342,6 +2343,180 @@ def bce_with_logits(input: torch.Tensor, target: torch.Tensor,
     return _BCELogitsFn.apply(input.contiguous(), target.to(torch.float32).contiguous(), div)
 
 
+def _loss_workspace(n: int, like: torch.Tensor) -> Optional[torch.Tensor]:
+    """The partial-record workspace of the reduced losses (None while one
+    workgroup finishes itself): torch.empty on the current stream, so a
+    captured step takes it from the graph pool."""
+    if n <= _lib.LOSS_ONE_LAUNCH_MAX:
+        return None
+    return torch.empty(LIB.hlhgat_loss_workspace_bytes(n), device=like.device, dtype=torch.uint8)
+
+
+class _BCEReduceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, mask, ignore_nan, red, alpha, gamma, scale):
+        n = x.numel()
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        ssum = torch.empty(1, device=x.device, dtype=torch.float32)
+        stats = torch.empty(4, device=x.device, dtype=torch.int64)
+        ws = _loss_workspace(n, x)
+        check(LIB.hlhgat_bce_reduce_fwd(x.data_ptr(), y.data_ptr(), _ptr(mask), n,
+                                        int(ignore_nan), red, alpha, gamma, scale, _ptr(ws),
+                                        0 if ws is None else ws.numel(), loss.data_ptr(),
+                                        ssum.data_ptr(), stats.data_ptr(), _stream(x)),
+              "bce_reduce_fwd")
+        ctx.mode = (int(ignore_nan), red, alpha, gamma, scale)
+        ctx.save_for_backward(x, y, mask, ssum, stats)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, _gstats):
+        x, y, mask, ssum, stats = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        check(LIB.hlhgat_bce_reduce_bwd(x.data_ptr(), y.data_ptr(), _ptr(mask), x.numel(),
+                                        *ctx.mode, ssum.data_ptr(), stats.data_ptr(),
+                                        g.data_ptr(), dx.data_ptr(), _stream(x)),
+              "bce_reduce_bwd")
+        return dx, None, None, None, None, None, None, None
+
+
+def bce_logits_loss(input: torch.Tensor, target: torch.Tensor,
+                    mask: Optional[torch.Tensor] = None, *, ignore_nan: bool = False,
+                    reduction: str = "mean", focal: Optional[Tuple[float, float, float]] = None,
+                    return_stats: bool = False):
+    """The torch expression
+
+        m = mask.bool() & ~isnan(target)      (each half only when asked for)
+        b = F.binary_cross_entropy_with_logits(input[m], target[m], reduction=reduction)
+
+    without the data-dependent gather: the selection is made on the device
+    inside the reduction (hlhgat_bce_reduce_fwd / _bwd), so the shapes are
+    static and the call captures into a hipGraph.  ``focal=(alpha, gamma,
+    scale)`` (with reduction "mean") returns scale * alpha * (1 - exp(-b)) **
+    gamma * b, the reference's FocalLoss (lib/Loss_function.py:14-26) with
+    scale = 1e4; gamma is 0 or >= 1.  The input gradient is exactly +0.0 at
+    excluded positions, whose input and target values (NaN, inf) enter nothing.
+
+    Unlike torch, an EMPTY selection gives loss 0 and a zero gradient, not
+    NaN: one all-missing batch must not poison Adam inside a captured step.
+
+    One or two launches forward (two above 16384 elements), one backward; the
+    result is a function of the inputs alone (fixed summation order, bitwise
+    equal eager or replayed).  A bool / uint8 mask is read as it is; any other
+    dtype costs one ATen launch (mask != 0).  No gradient flows into target or
+    mask.  ``return_stats=True`` also returns int64 [cnt, tp, fp, fn] over the
+    selection (prediction input > 0, positive target > 0.5): the counts the
+    TSP loop's F1 is built from (main_TSP...:346-347)."""
+    _req_dev(input, "input")
+    if input.shape != target.shape:
+        raise RuntimeError(f"hlhgat: bce_logits_loss shapes differ: {tuple(input.shape)} vs "
+                           f"{tuple(target.shape)}")
+    if target.requires_grad or (mask is not None and mask.requires_grad):
+        raise RuntimeError("hlhgat: bce_logits_loss: target / mask must not require grad")
+    if input.numel() == 0:
+        raise RuntimeError("hlhgat: bce_logits_loss of an empty tensor")
+    if focal is not None:
+        if reduction != "mean":
+            raise ValueError("hlhgat: bce_logits_loss: focal is a function of the mean")
+        alpha, gamma, scale = (float(v) for v in focal)
+        if not (gamma == 0.0 or gamma >= 1.0):
+            raise ValueError(f"hlhgat: bce_logits_loss: focal gamma {gamma} (0 or >= 1)")
+        red = _lib.LOSS_FOCAL
+    elif reduction in ("mean", "sum"):
+        alpha = gamma = scale = 0.0
+        red = _lib.LOSS_MEAN if reduction == "mean" else _lib.LOSS_SUM
+    else:
+        raise ValueError(f"hlhgat: bce_logits_loss reduction {reduction!r}")
+    if mask is not None:
+        if mask.shape != input.shape or mask.device != input.device:
+            raise RuntimeError(f"hlhgat: bce_logits_loss: mask {tuple(mask.shape)} on "
+                               f"{mask.device} does not match input {tuple(input.shape)}")
+        if mask.dtype == torch.bool:
+            mask = mask.contiguous().view(torch.uint8)
+        elif mask.dtype == torch.uint8:
+            mask = mask.contiguous()
+        else:
+            mask = (mask != 0).contiguous().view(torch.uint8)
+    loss, stats = _BCEReduceFn.apply(input.contiguous(), target.to(torch.float32).contiguous(),
+                                     mask, bool(ignore_nan), red, alpha, gamma, scale)
+    return (loss, stats) if return_stats else loss
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, label, ignore_index, red):
+        rows, cols = x.shape
+        ld = x.stride(0) if rows > 1 else cols
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        stats = torch.empty(2, device=x.device, dtype=torch.int64)
+        ws = _loss_workspace(rows, x)
+        check(LIB.hlhgat_cross_entropy_fwd(x.data_ptr(), ld, rows, cols, label.data_ptr(),
+                                           ignore_index, red, _ptr(ws),
+                                           0 if ws is None else ws.numel(), loss.data_ptr(),
+                                           stats.data_ptr(), _stream(x)), "cross_entropy_fwd")
+        ctx.args = (ld, rows, cols, ignore_index, red)
+        ctx.save_for_backward(x, label, stats)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, _gstats):
+        x, label, stats = ctx.saved_tensors
+        ld, rows, cols, ignore_index, red = ctx.args
+        g = g.contiguous()
+        dx = torch.empty((rows, cols), device=x.device, dtype=torch.float32)
+        check(LIB.hlhgat_cross_entropy_bwd(x.data_ptr(), ld, rows, cols, label.data_ptr(),
+                                           ignore_index, red, stats.data_ptr(), g.data_ptr(),
+                                           dx.data_ptr(), cols, _stream(x)),
+              "cross_entropy_bwd")
+        return dx, None, None, None
+
+
+def cross_entropy(input: torch.Tensor, label: torch.Tensor, *, ignore_index: int = -100,
+                  reduction: str = "mean", return_stats: bool = False):
+    """F.cross_entropy(input [R, C], label [R] of class indices, ignore_index=...,
+    reduction="mean" | "sum") for C <= 64 on the HIP path
+    (hlhgat_cross_entropy_fwd / _bwd): one or two launches forward (two above
+    16384 rows), one backward, fixed summation order.  "mean" divides by the
+    number of non-ignored rows, as torch does.  A column block of a wider
+    tensor (unit column stride) is read in place through its row stride; any
+    other layout is made contiguous first.
+
+    Unlike torch, all rows ignored gives loss 0 and a zero gradient, not NaN,
+    and a label that is neither ignore_index nor in [0, C) does not
+    device-assert: its row is ignored and the device error word is raised
+    (check_device_errors / TrainStep then raise RuntimeError).
+
+    No gradient flows into label.  ``return_stats=True`` also returns int64
+    [cnt, correct]: the non-ignored rows and those whose (lowest-index) argmax
+    is the label, the accuracy the CIFAR loop prints."""
+    _req_dev(input, "input")
+    if input.dim() != 2 or label.dim() != 1 or label.size(0) != input.size(0):
+        raise RuntimeError(f"hlhgat: cross_entropy wants input [R, C] and label [R], got "
+                           f"{tuple(input.shape)} and {tuple(label.shape)}")
+    if label.is_floating_point() or label.device != input.device:
+        raise RuntimeError("hlhgat: cross_entropy: label must hold class indices on the input's "
+                           "device")
+    rows, cols = input.shape
+    if rows == 0:
+        raise RuntimeError("hlhgat: cross_entropy of an empty tensor")
+    if not 1 <= cols <= _lib.CE_MAX_CLASSES:
+        raise RuntimeError(f"hlhgat: cross_entropy: C = {cols} outside [1, "
+                           f"{_lib.CE_MAX_CLASSES}] (hlhgat.nn.CrossEntropyLoss sends larger C "
+                           f"to torch)")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"hlhgat: cross_entropy reduction {reduction!r}")
+    red = _lib.LOSS_MEAN if reduction == "mean" else _lib.LOSS_SUM
+    x = input
+    if not (x.stride(1) == 1 and (rows == 1 or x.stride(0) >= cols)):
+        x = x.contiguous()
+    loss, stats = _CrossEntropyFn.apply(x, label.to(torch.int64).contiguous(), int(ignore_index),
+                                        red)
+    return (loss, stats) if return_stats else loss
+
+
 # ----------------------------------------------------------------------------
 # device error word (include/hlhgat.h: hlhgat_device_errors)
 # ----------------------------------------------------------------------------
@@ -2349,6 +2524,9 @@ _DEVERR_TEXT = {
     _lib.DEVERR_HODGE_SIZE: "hodge_build: a Laplacian row would end past the buffers sized "
                             "from the caller's sizes= (duplicate edges or self-loops?); the "
                             "row was not written",
+    _lib.DEVERR_LABEL: "cross_entropy (label bit): a label that is neither ignore_index nor "
+                       "a class index in [0, C); its row was left out of the loss and the "
+                       "gradient",
     _lib.DEVERR_BN_STATE: "BatchNorm: an arrival counter was found beyond its total (the "
                           "workspace was written by something else or shared by concurrent "
                           "launches); that launch's statistics are not trusted",

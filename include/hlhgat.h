@@ -823,6 +823,83 @@ int hlhgat_bce_logits_fwd(const float* x, const float* y, int64_t n, float div, 
 int hlhgat_bce_logits_bwd(const float* x, const float* y, int64_t n, float div,
                           const float* gout, float* dx, void* stream);
 
+/* ---- reduced training losses (csrc/loss.hip) ----------------------------- */
+/* Structure shared by the two families below.  No floating-point atomics and
+ * no hand-off between workgroups inside a launch: the forward is a grid kernel
+ * writing one 32-byte partial record per workgroup into `workspace`, then a
+ * one-workgroup finish kernel that sums the records in index order with a
+ * fixed tree.  The grid is min(ceil(n / 4096), 256) workgroups, a function of
+ * n alone (never of the device), each thread walking its elements in a fixed
+ * order; n <= 16384 runs as ONE self-finishing workgroup (one launch, the
+ * workspace may be NULL).  Results are therefore a function of the inputs:
+ * bitwise equal across runs, streams, pointer alignments, eager or replayed.
+ * hlhgat_loss_workspace_bytes(n): the bytes `workspace` must hold (16-byte
+ * aligned) for n elements (BCE) or n rows (cross-entropy).
+ * Empty selection (cnt == 0): loss = 0 and dx = 0 everywhere.  torch returns
+ * NaN for the mean of nothing; one all-missing batch must not poison Adam
+ * inside a captured step, so this library differs here on purpose.
+ * The backwards are one grid-stride elementwise launch reading the forward's
+ * device scalars (sum, stats[0]); gout is a device scalar. */
+#define HLHGAT_LOSS_MEAN 0
+#define HLHGAT_LOSS_SUM 1
+#define HLHGAT_LOSS_FOCAL 2
+size_t hlhgat_loss_workspace_bytes(int64_t n);
+
+/* BCE with logits over an on-device selection: the objective of the
+ * peptides-func loop, FocalLoss()(out[mask], y[mask]) with mask = ~isnan(y)
+ * (main_pepfunc...:179-186,267), of the TSP loop, FocalLoss() on the per-edge
+ * logits (main_TSP...:59-71,321,397), and lib/Loss_function.py:14-26, without
+ * the data-dependent boolean gather.  Element i is included iff (mask == NULL
+ * or mask[i] != 0) and not (ignore_nan and y_i is NaN); the x and y of an
+ * excluded element enter no sum.  With I the included set, cnt = |I|:
+ *   S = sum_{i in I} ((1 - y_i) x_i - log_sigmoid(x_i)),
+ *       log_sigmoid(x) = min(x, 0) - log1p(exp(-|x|));
+ *   SUM: loss = S;  MEAN: loss = S / cnt;
+ *   FOCAL: b = S / cnt, loss = scale alpha (1 - e^-b)^gamma b, 1 - e^-b taken
+ *       as -expm1f(-b); gamma = 0 (loss = scale alpha b) or gamma >= 1.
+ *   sum[0] = S; stats[0..3] = cnt, tp, fp, fn over I with prediction x > 0 and
+ *       positive label y > 0.5 (the F1 counts of main_TSP...:346-347);
+ *       per-workgroup counts are int32, the totals int64.
+ *   bwd: dx_i = gout c (sigmoid(x_i) - y_i) for i in I, +0.0 otherwise;
+ *       c = 1 (SUM), 1 / cnt (MEAN),
+ *       scale alpha ((1-pt)^gamma + gamma (1-pt)^(gamma-1) pt b) / cnt (FOCAL,
+ *       pt = e^-b); sigmoid(x) - y in hlhgat_bce_logits_bwd's stable form.
+ * 16-byte loads when x, y (dx) are 16-byte and mask 4-byte aligned, a scalar
+ * path otherwise, both in the same per-thread order. */
+int hlhgat_bce_reduce_fwd(const float* x, const float* y, const unsigned char* mask, int64_t n,
+                          int ignore_nan, int reduction, float alpha, float gamma, float scale,
+                          void* workspace, size_t workspace_bytes, float* loss, float* sum,
+                          int64_t* stats, void* stream);
+int hlhgat_bce_reduce_bwd(const float* x, const float* y, const unsigned char* mask, int64_t n,
+                          int ignore_nan, int reduction, float alpha, float gamma, float scale,
+                          const float* sum, const int64_t* stats, const float* gout, float* dx,
+                          void* stream);
+
+/* Cross-entropy over the rows of x [rows, cols] (row stride ldx >= cols: a
+ * column block of a wider tensor works), torch.nn.CrossEntropyLoss() of the
+ * CIFAR10SP loop (main_cifar10SP...:137,203); 1 <= cols <=
+ * HLHGAT_CE_MAX_CLASSES, one thread per row:
+ *   loss_r = log sum_j exp(x_rj - m_r) + m_r - x_{r,label_r}, m_r = max_j x_rj;
+ *   MEAN: loss = sum_valid loss_r / cnt (torch: the non-ignored rows);
+ *   SUM: loss = sum_valid loss_r;
+ *   stats[0..1] = cnt, correct (rows whose lowest-index maximum is the label:
+ *       the accuracy the loop prints);
+ *   bwd: dx_rj = gout / cnt (softmax_rj - [j == label_r]) (SUM: gout) on
+ *       valid rows, +0.0 on ignored rows; columns cols..lddx-1 of dx are
+ *       never written.
+ * A label equal to ignore_index is ignored.  A label that is neither that
+ * nor in [0, cols) is ignored too, indexes nothing, and raises
+ * HLHGAT_DEVERR_LABEL in the device error word (torch device-asserts). */
+#define HLHGAT_CE_MAX_CLASSES 64
+int hlhgat_cross_entropy_fwd(const float* x, int64_t ldx, int64_t rows, int64_t cols,
+                             const int64_t* label, int64_t ignore_index, int reduction,
+                             void* workspace, size_t workspace_bytes, float* loss,
+                             int64_t* stats, void* stream);
+int hlhgat_cross_entropy_bwd(const float* x, int64_t ldx, int64_t rows, int64_t cols,
+                             const int64_t* label, int64_t ignore_index, int reduction,
+                             const int64_t* stats, const float* gout, float* dx, int64_t lddx,
+                             void* stream);
+
 /* ---- workspaces --------------------------------------------------------- */
 /* Zero `bytes` (a multiple of 4) at p with a kernel on `stream` (graph-capture
  * safe; used to initialise the BatchNorm workspace counters). */
@@ -850,6 +927,9 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
 /* hlhgat_hodge_build: a row of L0 / L1 would end past the buffers the caller
  * sized (the row pointers do not describe a simple graph's Laplacians) */
 #define HLHGAT_DEVERR_HODGE_SIZE 2u
+/* hlhgat_cross_entropy_fwd: a label that is neither ignore_index nor a class
+ * index; its row was left out of the loss and the gradient */
+#define HLHGAT_DEVERR_LABEL 4u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 

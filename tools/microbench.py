@@ -111,12 +111,129 @@ def dropout_leg(rec, reps, dev):
             us, mn = timeit(fn, reps)
             rec(f"dropout_{name} {tag} [{n},{d}] eager call", us, mn, by)
 
+# the reduced losses: cross-entropy [R, C] at the config-3 batch sizes, BCE /
+# focal over the config-5 edge logits (4 graphs: 207000 with the padding of
+# the static-shape step, 206858 real edges -- not a multiple of 4)
+LOSS_CE_SHAPES = [(64, 10), (256, 10)]
+LOSS_BCE_SHAPES = [207000, 206858]
+
+
+def _ab(fa, fb, reps, rounds=5):
+    """Interleaved (a, b, a, b, ...) windows of `reps` timed calls each: the
+    per-window medians in us, their medians, a's spread and b over a."""
+    ms = {"a": [], "b": []}
+    for _ in range(rounds):
+        for k, fn in (("a", fa), ("b", fb)):
+            ms[k].append(round(timeit(fn, reps)[0], 2))
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    return {"us_aten": ms["a"], "us_hip": ms["b"], "median_us_aten": med["a"],
+            "median_us_hip": med["b"],
+            "spread_aten": round((max(ms["a"]) - min(ms["a"])) / med["a"], 4),
+            "hip_over_aten": round(med["b"] / med["a"], 4)}
+
+
+def loss_leg(rec, reps, dev):
+    """ops.cross_entropy and ops.bce_logits_loss (mean and focal, masked and
+    not) beside the ATen composition of the same objective.  "replayed": the
+    kernels alone through the C-ABI (20 forwards / backwards captured and
+    replayed), GB/s against the algorithmic bytes (forward: read x, y / label
+    [, mask]; backward: the same plus write dx).  "eager call": one forward,
+    or forward + backward through autograd, with its host enqueue; the A/B
+    windows of the two arms are interleaved."""
+    from hlhgat import _lib, ops
+    from hlhgat._lib import LIB, check
+    F = torch.nn.functional
+    gout = torch.ones(1, device=dev)
+    loss = torch.empty(1, device=dev)
+    ssum = torch.empty(1, device=dev)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def fwd_bwd(fn, x):
+        def run():
+            x.grad = None
+            fn().backward()
+        return run
+
+    for R, C in LOSS_CE_SHAPES:
+        x = torch.randn(R, C, device=dev, requires_grad=True)
+        xd = x.detach()
+        lab = torch.randint(0, C, (R,), device=dev)
+        dx = torch.empty(R, C, device=dev)
+
+        def cf():
+            check(LIB.hlhgat_cross_entropy_fwd(xd.data_ptr(), C, R, C, lab.data_ptr(), -100,
+                                               _lib.LOSS_MEAN, None, 0, loss.data_ptr(),
+                                               stats.data_ptr(), ops._stream(xd)), "ce_fwd")
+
+        def cb():
+            check(LIB.hlhgat_cross_entropy_bwd(xd.data_ptr(), C, R, C, lab.data_ptr(), -100,
+                                               _lib.LOSS_MEAN, stats.data_ptr(), gout.data_ptr(),
+                                               dx.data_ptr(), C, ops._stream(xd)), "ce_bwd")
+
+        for name, launch, by in (("fwd", cf, 4.0 * R * C + 8 * R),
+                                 ("bwd", cb, 8.0 * R * C + 8 * R)):
+            us, mn = replayed(launch, reps)
+            rec(f"cross_entropy_{name} hip [{R},{C}] replayed x20", us, mn, by)
+        hip = lambda: ops.cross_entropy(x, lab)  # noqa: E731
+        aten = lambda: F.cross_entropy(x, lab)  # noqa: E731
+        for name, fa, fb in (("fwd", aten, hip), ("fwd+bwd", fwd_bwd(aten, x), fwd_bwd(hip, x))):
+            r = _ab(fa, fb, reps)
+            rec(f"cross_entropy_{name} [{R},{C}] eager call, aten vs hip", r["median_us_hip"],
+                min(r["us_hip"]), None, None, **r)
+
+    for n in LOSS_BCE_SHAPES:
+        x = torch.randn(n, device=dev, requires_grad=True)
+        xd = x.detach()
+        y = (torch.rand(n, device=dev) > 0.5).float()
+        mask = torch.rand(n, device=dev) > 0.1
+        dx = torch.empty(n, device=dev)
+        ws = torch.empty(LIB.hlhgat_loss_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        for mtag, mk in (("", None), (" masked", mask)):
+            mp = None if mk is None else mk.data_ptr()
+            for otag, red, focal in (("bce_mean", _lib.LOSS_MEAN, None),
+                                     ("focal", _lib.LOSS_FOCAL, (0.25, 2.0, 1e4))):
+                mode = (0, red, 0.25, 2.0, 1e4)
+
+                def bf():
+                    check(LIB.hlhgat_bce_reduce_fwd(xd.data_ptr(), y.data_ptr(), mp, n, *mode,
+                                                    ws.data_ptr(), ws.numel(), loss.data_ptr(),
+                                                    ssum.data_ptr(), stats.data_ptr(),
+                                                    ops._stream(xd)), "bce_reduce_fwd")
+
+                def bb():
+                    check(LIB.hlhgat_bce_reduce_bwd(xd.data_ptr(), y.data_ptr(), mp, n, *mode,
+                                                    ssum.data_ptr(), stats.data_ptr(),
+                                                    gout.data_ptr(), dx.data_ptr(),
+                                                    ops._stream(xd)), "bce_reduce_bwd")
+
+                nm = 0 if mk is None else n
+                for name, launch, by in (("fwd (2 launches)", bf, 8.0 * n + nm),
+                                         ("bwd", bb, 12.0 * n + nm)):
+                    us, mn = replayed(launch, reps)
+                    rec(f"{otag}_{name} hip{mtag} [{n}] replayed x20", us, mn, by)
+
+                def aten():
+                    xs, ys = (x, y) if mk is None else (x[mk], y[mk])
+                    b = F.binary_cross_entropy_with_logits(xs, ys)
+                    if focal is None:
+                        return b
+                    logpt = -b  # lib/Loss_function.py:22-26
+                    pt = torch.exp(logpt)
+                    return -((1 - pt) ** focal[1]) * focal[0] * logpt * focal[2]
+
+                hip = lambda: ops.bce_logits_loss(x, y, mk, focal=focal)  # noqa: E731
+                for name, fa, fb in (("fwd", aten, hip),
+                                     ("fwd+bwd", fwd_bwd(aten, x), fwd_bwd(hip, x))):
+                    r = _ab(fa, fb, reps)
+                    rec(f"{otag}_{name}{mtag} [{n}] eager call, aten vs hip", r["median_us_hip"],
+                        min(r["us_hip"]), None, None, **r)
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "gpurun_out", "microbench.json"))
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", choices=("dropout",), default=None,
+    ap.add_argument("--only", choices=("dropout", "loss"), default=None,
                     help="run this leg alone (default: every leg)")
     args = ap.parse_args()
     from hlhgat import ops
@@ -143,8 +260,8 @@ def main():
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
 
-    if args.only == "dropout":
-        dropout_leg(rec, args.reps, dev)
+    if args.only in ("dropout", "loss"):
+        (dropout_leg if args.only == "dropout" else loss_leg)(rec, args.reps, dev)
         save()
         return
 
@@ -244,6 +361,9 @@ def main():
 
     # ---- dropout ----------------------------------------------------------
     dropout_leg(rec, args.reps, dev)
+
+    # ---- reduced losses ---------------------------------------------------
+    loss_leg(rec, args.reps, dev)
     save()
 
 
