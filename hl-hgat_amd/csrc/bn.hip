@@ -16,16 +16,23 @@
 // barrier, sums ALL partials itself in a fixed order (flat_reduce), and
 // normalises from the registers -- no second read of x, no last-arriver tail,
 // no flag hand-off.  Workgroup 0 of a tile writes the saved and running
-// statistics.  (The same structure for the backward ran 12 % faster alone,
-// 31.8 vs 35.5 us per fwd+bwd at the ZINC shape, but made the training step
-// 1.2 % SLOWER in a same-box A/B -- its register-heavy workgroups wait at the
-// barrier while the other stream's kernels need the CUs -- so it was removed.)
+// statistics.
 //
-// Otherwise, and always for the backward: two launches, k_bn_stats /
-// k_bn_bwd_reduce (the last workgroup to arrive sums the partials -- in the
-// same flat order up to kFlatMax partitions, so both forward paths give
-// bitwise the same results; a two-level last-arriver tree above) then
-// k_bn_apply / k_bn_bwd_apply.
+// Backward in ONE launch (k_bn_bwd_grid, hlhgat_set_bn_bwd_one_launch): the
+// geometry, arithmetic and reduction tree of k_bn_bwd_reduce, with the masked
+// gradient and x - mean of a workgroup's rows kept in registers; the last
+// arriver of the tree publishes dx's coefficients by bumping the tile's
+// generation word (the hand-over protocol of k_proj_bn_fwd) and the others
+// store dx from their registers -- no second read of x, dy and y, no apply
+// launch.  Bitwise the two-launch results.  (A first version with a flat
+// barrier, before the two chains and the captured step, ran 12 % faster
+// alone but 1.2 % slower in the step and was removed; DESIGN.md §23 has the
+// measurements of this one.)
+//
+// Otherwise: two launches, k_bn_stats / k_bn_bwd_reduce (the last workgroup
+// to arrive sums the partials -- in the same flat order up to kFlatMax
+// partitions, so both forward paths give bitwise the same results; a
+// two-level last-arriver tree above) then k_bn_apply / k_bn_bwd_apply.
 //
 // Arithmetic (both paths): mean = S0/n, var = S1/n - mean^2 (fp64),
 // invstd = 1/sqrt(var + eps); y = relu?((x - mean) * w invstd + b);
@@ -272,7 +279,7 @@ __device__ unsigned g_bn_log_n = 0;
 __device__ hlhgat_bn_giveup_t g_bn_log[HLHGAT_BN_LOG_MAX];
 
 constexpr uint64_t kTicksPerUs = 100;  // s_memrealtime runs at 100 MHz
-enum : unsigned { kKidBnGrid = 1, kKidProjBn = 2 };
+enum : unsigned { kKidBnGrid = 1, kKidProjBn = 2, kKidBnBwd = 3 };
 
 __device__ __forceinline__ void report_state_error(unsigned* err) {
   if (err) __hip_atomic_store(err, (unsigned)HLHGAT_DEVERR_BN_STATE, __ATOMIC_RELAXED,
@@ -904,6 +911,13 @@ void launch_bwd_reduce(bool vec, dim3 grid, hipStream_t st, ProfScope* prof, con
     launch(k_bn_bwd_reduce<1>, grid, dim3(kThreads), 0, st, prof, s);
 }
 
+// dx of one element from the masked gradient g and xc = x - mean: the ONE
+// expression of k_bn_bwd_apply and k_bn_bwd_grid (the same operations, so the
+// same bits whichever kernel writes a row).
+__device__ __forceinline__ float bn_dx(float A, float g, float B, float xc, float Cc) {
+  return A * g + (B * xc + Cc);
+}
+
 template <int V>
 __device__ __forceinline__ void k_bn_bwd_apply_body(const BwdApplyArgs& a, Blk blk) {
   using vt = typename VecT<V>::type;
@@ -940,7 +954,7 @@ __device__ __forceinline__ void k_bn_bwd_apply_body(const BwdApplyArgs& a, Blk b
     for (int v = 0; v < V; ++v) {
       float g = vget(gv[u], v);
       if (a.y && !(vget(yv[u], v) > 0.f)) g = 0.f;
-      vget(o, v) = r >= n_eff ? 0.f : A[v] * g + (B[v] * (vget(xv[u], v) - mu[v]) + Cc[v]);
+      vget(o, v) = r >= n_eff ? 0.f : bn_dx(A[v], g, B[v], vget(xv[u], v) - mu[v], Cc[v]);
     }
     vstore<V>(a.dx + r * a.lddx + c, o);
   }
@@ -1470,7 +1484,226 @@ __global__ __launch_bounds__(kThreads) void k_proj_bn_fwd(ProjBnArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// BatchNorm backward in ONE launch (hlhgat_bn_bwd_train)
+//
+// The grid, the threads' rows and the arithmetic of k_bn_bwd_reduce; thread
+// (rg, cl) owns rows r_lo + rg + j * rp (j < RPT) of its partition:
+//   1. each owned row's x, dy (and y) is loaded once; the masked gradient g
+//      and xc = x - mean stay in registers, the fp64 partials are summed in
+//      ascending row order (k_bn_bwd_reduce_body's operations) and written
+//      through;
+//   2. last_reduce's tree, unchanged; its last arriver forms dweight, dbias
+//      and dx's coefficients, writes the coefficients through, drains the
+//      stores and bumps the tile's generation word;
+//   3. every other workgroup read the generation before it arrived; it polls
+//      the word for at most wait_us, loads the coefficients and stores dx of
+//      its rows from the registers (padding rows as 0).  A workgroup whose
+//      wait runs out leaves its rows to the finaliser (give_up / take_left,
+//      the protocol above), which computes their dx from x, dy and y in
+//      memory with the same operations.
+// The finaliser is whichever workgroup arrives last and never waits; every
+// wait is bounded and ends in a hand-over; nothing depends on co-residency.
+// ---------------------------------------------------------------------------
+template <int V, int RPT>
+__device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) {
+  using vt = typename VecT<V>::type;
+  constexpr int CH = RPT < 4 ? RPT : 4;  // rows (3 loads each) in flight, as k_bn_bwd_reduce
+  __shared__ unsigned s_gen0, s_ok;
+  const int cl = threadIdx.x % a.tpr;
+  const int rg = threadIdx.x / a.tpr;
+  const int c0 = blk.y * a.tpr * V;
+  const int c = c0 + cl * V;
+  const int64_t r_lo = (int64_t)blk.x * a.rows_per_part;
+  const int64_t n_eff = eff_rows(a.n, a.nvalid);
+  int64_t r_hi = r_lo + a.rows_per_part;
+  if (r_hi > n_eff) r_hi = n_eff;
+  vt gr[RPT], xcr[RPT];
+  double s0[V], s1[V];
+  float mu[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    s0[v] = s1[v] = 0.0;
+    mu[v] = (c + v < a.C) ? a.save_mean[c + v] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < RPT; ++j)
+#pragma unroll
+    for (int v = 0; v < V; ++v) vget(gr[j], v) = vget(xcr[j], v) = 0.f;
+  // the ReLU mask's source; without one (y == NULL) dy is read in its place and
+  // never tested, so every load below is unconditional and a chunk's loads are
+  // all in flight together
+  const bool has_y = a.y != nullptr;
+  const float* mp = has_y ? a.y : a.dy;
+  const int64_t ldm = has_y ? a.ldy : a.lddy;
+  if (c < a.C) {
+#pragma unroll
+    for (int j0 = 0; j0 < RPT; j0 += CH) {
+      vt xv[CH], gv[CH], yv[CH];
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {
+        const int64_t r = r_lo + rg + (int64_t)(j0 + u) * a.rp;
+        const int64_t rr = r < r_hi ? r : 0;  // branch-free: rows past the end read row 0
+        xv[u] = vload<V>(a.x + rr * a.ldx + c);
+        gv[u] = vload<V>(a.dy + rr * a.lddy + c);
+        yv[u] = vload<V>(mp + rr * ldm + c);
+      }
+#pragma unroll
+      for (int u = 0; u < CH; ++u) {  // row order, as k_bn_bwd_reduce
+        const int64_t r = r_lo + rg + (int64_t)(j0 + u) * a.rp;
+        if (r < r_hi) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            float g = vget(gv[u], v);
+            if (has_y && !(vget(yv[u], v) > 0.f)) g = 0.f;
+            const float xc = vget(xv[u], v) - mu[v];
+            vget(gr[j0 + u], v) = g;
+            vget(xcr[j0 + u], v) = xc;
+            s0[v] += (double)g;
+            s1[v] += (double)g * (double)xc;
+          }
+        }
+      }
+    }
+  }
+  // the finaliser's per-column inputs, fetched before the tree (off its critical path)
+  const int tile_c = a.tpr * V;
+  const int fc = c0 + (int)threadIdx.x;
+  const bool fcol = (int)threadIdx.x < tile_c && fc < a.C;
+  const float f_is = fcol ? a.save_invstd[fc] : 0.f;
+  const float f_w = (fcol && a.weight) ? a.weight[fc] : 1.f;
+  write_partials<V, kThreads>(s0, s1, a, c0, blk);
+  unsigned long long* word = gen_word(a, blk.y);
+  if (threadIdx.x == 0)  // the generation before this workgroup's arrival
+    s_gen0 = (unsigned)(__hip_atomic_load((gu64c_t*)word, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_AGENT) >> 32);
+  __shared__ double sum0[kThreads], sum1[kThreads];
+  __shared__ float sA[kThreads], sB[kThreads], sC[kThreads];
+  unsigned long long* tile_slots = a.slots + (int64_t)blk.y * blk.gx;
+  const bool fin = last_reduce<kThreads>(a, c0, tile_c, sum0, sum1, blk);
+  if (fin) {
+    if ((int)threadIdx.x < tile_c) {  // tile_c <= kThreads: one column per thread
+      const int t = threadIdx.x, cc = fc;
+      float A = 0.f, B = 0.f, Cc = 0.f;
+      if (fcol) {
+        bwd_coefs(f_is, f_w, sum0[t], sum1[t], n_eff, A, B, Cc);
+        if (a.dweight) a.dweight[cc] = (float)(sum1[t] * (double)f_is);
+        if (a.dbias) a.dbias[cc] = (float)sum0[t];
+        __hip_atomic_store(reinterpret_cast<unsigned*>(a.coef + cc), __float_as_uint(A),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(reinterpret_cast<unsigned*>(a.coef + a.C + cc), __float_as_uint(B),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(reinterpret_cast<unsigned*>(a.coef + 2 * a.C + cc),
+                           __float_as_uint(Cc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      sA[t] = A;
+      sB[t] = B;
+      sC[t] = Cc;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) publish_gen(word, 1ull << 32);  // completed (see take_left)
+  } else {
+    if (threadIdx.x == 0) {
+      unsigned ok = poll_gen(word, s_gen0, a.wait_us) ? 1u : 0u;
+      if (!ok) {
+        const unsigned total = a.parts <= a.flat_max
+                                   ? (unsigned)a.parts
+                                   : (unsigned)((a.parts + kGroup - 1) / kGroup);
+        ok = give_up(word, tile_slots + blk.x, s_gen0, kKidBnBwd, a.count + blk.y, false, total,
+                     a.wait_us)
+                 ? 1u
+                 : 0u;
+      }
+      s_ok = ok;
+    }
+    __syncthreads();
+    if (!s_ok) return;  // the finaliser computes these rows' dx from memory
+    for (int t = threadIdx.x; t < tile_c; t += kThreads) {
+      const int cc = c0 + t;
+      float A = 0.f, B = 0.f, Cc = 0.f;
+      if (cc < a.C) {
+        A = __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned*>(a.coef + cc),
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        B = __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned*>(a.coef + a.C + cc),
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        Cc = __uint_as_float(__hip_atomic_load(reinterpret_cast<unsigned*>(a.coef + 2 * a.C + cc),
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      }
+      sA[t] = A;
+      sB[t] = B;
+      sC[t] = Cc;
+    }
+  }
+  __syncthreads();
+  float A[V], B[V], Cc[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    A[v] = sA[cl * V + v];
+    B[v] = sB[cl * V + v];
+    Cc[v] = sC[cl * V + v];
+  }
+  if (c < a.C) {  // dx of the owned rows from the registers; output rows stop at n
+    int64_t r_end = r_lo + a.rows_per_part;
+    if (r_end > a.n) r_end = a.n;
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      const int64_t r = r_lo + rg + (int64_t)j * a.rp;
+      if (r < r_end) {
+        vt o;
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+          vget(o, v) =
+              r >= n_eff ? 0.f : bn_dx(A[v], vget(gr[j], v), B[v], vget(xcr[j], v), Cc[v]);
+        vstore<V>(a.out + r * a.ldo + c, o);
+      }
+    }
+  }
+  if (!fin) return;
+  // rows of partitions whose owners gave up: from x, dy, y in memory, same operations
+  __shared__ unsigned char taken[kMaxParts];
+  if (!take_left<kThreads>(tile_slots, (int)blk.gx, s_gen0, taken)) return;
+  if (c >= a.C) return;
+  for (unsigned p = 0; p < blk.gx; ++p) {
+    if (!taken[p]) continue;
+    const int64_t p_lo = (int64_t)p * a.rows_per_part;
+    int64_t p_end = p_lo + a.rows_per_part;
+    if (p_end > a.n) p_end = a.n;
+    for (int64_t r = p_lo + rg; r < p_end; r += a.rp) {
+      vt o;
+      if (r < n_eff) {
+        vt xv = vload<V>(a.x + r * a.ldx + c);
+        vt gv = vload<V>(a.dy + r * a.lddy + c);
+        vt yv = gv;
+        if (a.y) yv = vload<V>(a.y + r * a.ldy + c);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          float g = vget(gv, v);
+          if (a.y && !(vget(yv, v) > 0.f)) g = 0.f;
+          vget(o, v) = bn_dx(A[v], g, B[v], vget(xv, v) - mu[v], Cc[v]);
+        }
+      } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) vget(o, v) = 0.f;
+      }
+      vstore<V>(a.out + r * a.ldo + c, o);
+    }
+  }
+}
+
+template <int V, int RPT>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_grid(StatsArgs a) {
+  k_bn_bwd_grid_body<V, RPT>(a, blk_hw());
+}
+
 bool& proj_bn_fused_flag() {
+  static bool v = true;
+  return v;
+}
+
+// hlhgat_set_bn_bwd_one_launch(0): the backward as k_bn_bwd_reduce +
+// k_bn_bwd_apply even where k_bn_bwd_grid fits (bitwise the same results).
+bool& bn_bwd_one_launch_flag() {
   static bool v = true;
   return v;
 }
@@ -1592,6 +1825,36 @@ GridFn pick_grid(const BnLayout& L, bool vec) {
   return f;
 }
 
+GridFn bwd_grid_fn(bool vec, int rpt) {
+  switch (rpt * 2 + (vec ? 1 : 0)) {
+    case 4: return k_bn_bwd_grid<1, 2>;
+    case 5: return k_bn_bwd_grid<4, 2>;
+    case 8: return k_bn_bwd_grid<1, 4>;
+    case 9: return k_bn_bwd_grid<4, 4>;
+    case 16: return k_bn_bwd_grid<1, 8>;
+    case 17: return k_bn_bwd_grid<4, 8>;
+    case 32: return k_bn_bwd_grid<1, 16>;
+    case 33: return k_bn_bwd_grid<4, 16>;
+    case 64: return k_bn_bwd_grid<1, 32>;
+    case 65: return k_bn_bwd_grid<4, 32>;
+    default: return nullptr;
+  }
+}
+
+// The one-launch backward kernel for the backward's own layout, or nullptr
+// (k_bn_bwd_reduce + k_bn_bwd_apply): both switches on, a thread's rows fit
+// the registers, the grid at most 256 workgroups and the kernel's share of the
+// chip (capacity_of).  Its partials go through last_reduce's tree, so the
+// partition count itself is not capped at kFlatMax.
+GridFn pick_bwd_grid(const BnLayout& L, bool vec) {
+  if (!bn_one_launch() || !bn_bwd_one_launch_flag()) return nullptr;
+  const int64_t grid = (int64_t)L.parts * L.tiles;
+  const int rpt = rpt_bucket(L);
+  GridFn f = rpt ? bwd_grid_fn(vec, rpt) : nullptr;
+  const int64_t cap = f ? capacity_of(reinterpret_cast<const void*>(f)) : 0;
+  if (!f || grid > 256 || grid > cap) return nullptr;
+  return f;
+}
 
 }  // namespace
 
@@ -1917,6 +2180,17 @@ extern "C" int hlhgat_bn_bwd_train(const float* x, int64_t ldx, const float* y,
   s.dbias = dbias;
   hipStream_t st = as_stream(stream);
   dim3 g1(L.parts, L.tiles);
+  if (GridFn f = pick_bwd_grid(L, vec)) {  // one launch: reduce, coefficients and dx
+    s.out = dx;
+    s.ldo = lddx;
+    s.wait_us = g_wait_us;
+    HLH_CHECK_ARG(s.err, "bn_bwd_train: no device error word (%s)", hlhgat_last_error());
+    // algorithmic bytes: x, dy (and y) read once, dx written once
+    ProfScope prof(HLHGAT_PROF_BN_BWD, st, (y ? 16.0 : 12.0) * (double)n * C, 0.0);
+    launch(f, g1, dim3(kThreads), 0, st, &prof, s);
+    HLH_CHECK_LAUNCH();
+    return HLHGAT_OK;
+  }
   {  // algorithmic bytes of the reduction: x, dy (and y for the ReLU mask) read once
     ProfScope prof(HLHGAT_PROF_BN_BWD, st, (y ? 12.0 : 8.0) * (double)n * C, 0.0);
     if (vec)
@@ -2133,6 +2407,13 @@ extern "C" int hlhgat_set_bn_one_launch(int on) {
 }
 
 extern "C" int hlhgat_get_bn_one_launch(void) { return bn_one_launch_flag() ? 1 : 0; }
+
+extern "C" int hlhgat_set_bn_bwd_one_launch(int on) {
+  bn_bwd_one_launch_flag() = on != 0;
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_get_bn_bwd_one_launch(void) { return bn_bwd_one_launch_flag() ? 1 : 0; }
 
 extern "C" int hlhgat_set_bn_wait_us(unsigned wait_us) {
   g_wait_us = wait_us;

@@ -99,6 +99,8 @@ SIGNATURES = {
     "hlhgat_proj_bn_fused_capacity": (c_i32, [P_i64]),
     "hlhgat_set_bn_one_launch": (c_i32, [c_i32]),
     "hlhgat_get_bn_one_launch": (c_i32, []),
+    "hlhgat_set_bn_bwd_one_launch": (c_i32, [c_i32]),
+    "hlhgat_get_bn_bwd_one_launch": (c_i32, []),
     "hlhgat_set_bn_wait_us": (c_i32, [C.c_uint32]),
     "hlhgat_set_proj_bn_stamps": (c_i32, [c_vp, c_i64]),
     "hlhgat_bn_giveup_log": (c_i32, [c_vp, c_i32, c_vp]),

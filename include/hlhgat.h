@@ -697,6 +697,18 @@ int hlhgat_set_proj_bn_stamps(void* buf, int64_t words);
 int hlhgat_proj_bn_fused_capacity(int64_t* out);
 int hlhgat_set_bn_one_launch(int on);
 int hlhgat_get_bn_one_launch(void);
+/* BatchNorm backward (hlhgat_bn_bwd_train) in one launch (k_bn_bwd_grid: the
+ * reduction's grid keeps each row's masked gradient and x - mean in
+ * registers, the last arriver of the reduction tree publishes dx's
+ * coefficients and every workgroup stores dx of its own rows; the bounded
+ * wait and hand-over of the forward kernels) instead of the reduction and the
+ * apply launch; default 1.  Taken when hlhgat_set_bn_one_launch is on too
+ * (0 there turns off both directions), a thread's rows fit the registers
+ * (<= 32) and the grid is at most 256 workgroups and at most the kernel's
+ * share of the resident capacity.  0: the two launches; both give bitwise
+ * the same dx, dweight and dbias. */
+int hlhgat_set_bn_bwd_one_launch(int on);
+int hlhgat_get_bn_bwd_one_launch(void);
 /* Microseconds a one-launch BatchNorm workgroup waits for its tile's
  * statistics before it hands its rows to the finaliser (default 1000; 0 =
  * hand over at once unless already final: a test hook that forces the
@@ -712,10 +724,11 @@ int hlhgat_bn_wait_timeouts(unsigned* out);
  * what is copied); out[0 .. min(*logged, max, HLHGAT_BN_LOG_MAX)). */
 #define HLHGAT_BN_LOG_MAX 64
 typedef struct {
-  uint32_t kernel;    /* 1 = k_bn_fwd_grid, 2 = k_proj_bn_fwd */
+  uint32_t kernel;    /* 1 = k_bn_fwd_grid, 2 = k_proj_bn_fwd, 3 = k_bn_bwd_grid */
   uint32_t tile;      /* column tile (blockIdx.y) */
   uint32_t block;     /* row partition / row block (blockIdx.x) */
-  uint32_t total;     /* arrivals the finaliser needs (workgroups; groups for k_proj_bn_fwd) */
+  uint32_t total;     /* arrivals the finaliser needs (workgroups; groups for k_proj_bn_fwd
+                         and for k_bn_bwd_grid above its flat limit) */
   uint32_t arrivals;  /* arrivals counted when the wait ran out */
   uint32_t gen0;      /* the tile's generation when the workgroup arrived */
   uint32_t gen_seen;  /* the generation read after giving up */

@@ -18,6 +18,8 @@ Variants (A/B hooks, not product settings):
   splitbn     projection + BatchNorm as the projection with a statistics epilogue
               (no wait) + the apply launch
   nobarrier   twolaunchbn + splitbn: no kernel of the step waits for another workgroup
+  twolaunchbnbwd  the BatchNorm backward as reduction + apply launches (the forward
+              keeps its one launch)
 """
 import argparse
 import json
@@ -41,6 +43,7 @@ def set_variant(name, on):
     _lib.LIB.hlhgat_set_proj_bn_fused(0 if (on and name == "nofusedbn") else 1)
     _lib.LIB.hlhgat_set_proj_bwd_rows(0 if (on and name == "norows") else 1)
     _lib.LIB.hlhgat_set_bn_one_launch(0 if (on and name in ("twolaunchbn", "nobarrier")) else 1)
+    _lib.LIB.hlhgat_set_bn_bwd_one_launch(0 if (on and name == "twolaunchbnbwd") else 1)
     _lib.LIB.hlhgat_set_proj_bn_split(1 if (on and name in ("splitbn", "nobarrier")) else 0)
     from hlhgat import nn as hnn, hodge_st_model, train
     hnn.MLP_PAIRS = not (on and name == "nomlp2")
@@ -54,6 +57,8 @@ def main():
     ap.add_argument("variants", nargs="+")
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--gate", nargs=2, metavar=("ON", "OFF"),
+                    help="variants ON1 OFF1 ON2 OFF2 were given: also print tools/ab_gate.py's line")
     args = ap.parse_args()
     import bench
     import hlhgat
@@ -88,6 +93,10 @@ def main():
     out = {v: {"ms_median": sorted(x)[len(x) // 2], "ms_min": min(x),
                "ms": [round(t, 4) for t in x]} for v, x in res.items()}
     print(json.dumps(out))
+    if args.gate:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import ab_gate
+        print(json.dumps(ab_gate.gate(out, args.gate[0], args.gate[1])))
 
 
 if __name__ == "__main__":

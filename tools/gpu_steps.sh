@@ -10,6 +10,7 @@
 #   pmcstep the config-2 step under rocprofv3 --pmc (serialised dispatch)
 #   prof    rocprofv3 kernel stats + step census of the replayed bench
 #   pmc     FETCH / WRITE passes for the roofline traffic
+#   abbnbwd same-process A/B of the one-launch BatchNorm backward against two launches
 #   census  bench line with heads: k_poly_step per call site (tools/poly_census.py)
 # Stops at the first crash / time-out.
 set -u
@@ -175,6 +176,7 @@ for s in "$@"; do
     ab) step ab 900 python3 tools/ab_step.py base1 splitbn twolaunchbn nobarrier base2 --rounds 5 ;;
     big) step bigtests 400 $PT tests/test_proj_big.py -m gpu -v -s
          step bigbench 400 python3 tools/kbench.py --big --reps 10 --chain 5 ;;
+    abbnbwd) step abbnbwd 900 python3 tools/ab_step.py base1 twolaunchbnbwd1 base2 twolaunchbnbwd2 --rounds 6 --gate base twolaunchbnbwd ;;
     kbench) step kbench 300 python3 tools/kbench.py --only "proj" --reps 20 --chain 20 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac

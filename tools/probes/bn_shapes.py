@@ -1,7 +1,10 @@
 """BatchNorm kernels alone at the config-2 / config-5 shapes: each C-ABI call
 replayed 20x in a captured hipGraph (events around the replays), µs per call
 and GB/s on the algorithmic bytes (stats 4nC, apply 8nC, backward reduction
-12nC: x, dy, y; backward apply 16nC: x, dy, y read, dx written).
+12nC: x, dy, y; backward apply 16nC: x, dy, y read, dx written).  "bwd" is
+the backward as reduction + apply (hlhgat_set_bn_bwd_one_launch(0)), "bwd_one"
+hlhgat_bn_bwd_train as it selects by itself: k_bn_bwd_grid (16nC) where the
+layout fits, the same two launches elsewhere.
 
     python3 tools/probes/bn_shapes.py [--reps 10] [--chain 20]
 """
@@ -53,6 +56,7 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device="cpu").manual_seed(0)
     for n, C, tag in [(23157, 64, "cfg2 nodes"), (24868, 64, "cfg2 edges"),
+                      (1000, 256, "cfg2 readout"),
                       (40448, 32, "cfg5 nodes"), (40448, 128, "cfg5 nodes"),
                       (207360, 32, "cfg5 edges"), (207360, 64, "cfg5 edges"),
                       (207360, 128, "cfg5 edges"), (143360, 64, "cfg3 edges"),
@@ -109,10 +113,18 @@ def main():
         torch.cuda.synchronize()
         nC = float(n) * C
         r = {"shape": tag, "n": n, "C": C}
-        for name, fn, by in (("stats", stats, 4 * nC), ("apply", apply, 8 * nC),
-                             ("fwd", fwd, None), ("bwd_reduce", bred, 12 * nC),
-                             ("bwd", bwd, 28 * nC)):
-            us = timed(fn, args.reps, args.chain)
+        # "bwd": reduction + apply (the switch off); "bwd_one": hlhgat_bn_bwd_train
+        # as it selects by itself (k_bn_bwd_grid where the layout fits, else the
+        # same two launches)
+        prior = int(L.hlhgat_get_bn_bwd_one_launch())
+        for name, fn, by, one in (("stats", stats, 4 * nC, prior), ("apply", apply, 8 * nC, prior),
+                                  ("fwd", fwd, None, prior), ("bwd_reduce", bred, 12 * nC, prior),
+                                  ("bwd", bwd, 28 * nC, 0), ("bwd_one", bwd, 16 * nC, 1)):
+            L.hlhgat_set_bn_bwd_one_launch(one)
+            try:
+                us = timed(fn, args.reps, args.chain)
+            finally:
+                L.hlhgat_set_bn_bwd_one_launch(prior)
             r[name + "_us"] = round(us, 2)
             if by:
                 r[name + "_GBps"] = round(by / us / 1e3, 1)
