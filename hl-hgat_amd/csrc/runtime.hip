@@ -298,12 +298,20 @@ struct AdamArgs {
   float* step;
   double lr, beta1, beta2, eps, wd;
   int prepared;  // *step already holds this update's count (hlhgat_adam_prepare)
+  const double* lr_dev;  // kDevLr: the learning rate, read on the device
 };
 
+// kDevLr: the learning rate is *a.lr_dev (one fp64 load per workgroup, beside
+// the step count) instead of the by-value a.lr, so a captured launch follows a
+// scheduler; every expression below is the same double arithmetic on it, so
+// equal values give equal bits.
+template <bool kDevLr>
 __global__ __launch_bounds__(256) void k_adam_flat(AdamArgs a) {
   // bias corrections once per workgroup (fp64 pow), broadcast through LDS
   __shared__ float sh[2];
+  __shared__ double sh_lr;
   if (threadIdx.x == 0) {
+    if constexpr (kDevLr) sh_lr = *a.lr_dev;
     // torch: state_steps += 1 (fp32), then the update
     const float s = a.prepared ? *a.step : *a.step + 1.0f;
     const double bc1 = 1.0 - pow(a.beta1, (double)s);
@@ -314,6 +322,8 @@ __global__ __launch_bounds__(256) void k_adam_flat(AdamArgs a) {
   __syncthreads();
   const float bias_correction1 = sh[0];
   const float bias_correction2_sqrt = sh[1];
+  double lr = a.lr;
+  if constexpr (kDevLr) lr = sh_lr;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n;
        i += (int64_t)gridDim.x * 256) {
     float param = a.p[i];
@@ -323,7 +333,7 @@ __global__ __launch_bounds__(256) void k_adam_flat(AdamArgs a) {
     if (a.wd != 0.0) grad += param * a.wd;
     exp_avg = a.beta1 * exp_avg + (1 - a.beta1) * grad;
     exp_avg_sq = a.beta2 * exp_avg_sq + (1 - a.beta2) * grad * grad;
-    const float step_size = a.lr / bias_correction1;
+    const float step_size = lr / bias_correction1;
     const float denom = (sqrtf(exp_avg_sq) / bias_correction2_sqrt) + a.eps;
     param -= step_size * exp_avg / denom;
     a.p[i] = param;
@@ -356,20 +366,37 @@ extern "C" int hlhgat_adam_prepare(float* grad, int64_t n, float* step, void* st
   return HLHGAT_OK;
 }
 
+namespace {
+int adam_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                float* step, double lr, const double* lr_dev, double beta1, double beta2,
+                double eps, double weight_decay, int prepared, hipStream_t s) {
+  if (n > 0) {
+    int64_t g = ceil_div(n, 256 * 2);
+    if (g > 2048) g = 2048;
+    AdamArgs a{param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2,
+               eps, weight_decay, prepared, lr_dev};
+    if (lr_dev)
+      launch(k_adam_flat<true>, dim3((unsigned)g), dim3(256), 0, s, nullptr, a);
+    else
+      launch(k_adam_flat<false>, dim3((unsigned)g), dim3(256), 0, s, nullptr, a);
+    HLH_CHECK_LAUNCH();
+  }
+  if (!prepared) {
+    launch(k_adam_step_inc, dim3(1), dim3(1), 0, s, nullptr, step);
+    HLH_CHECK_LAUNCH();
+  }
+  return HLHGAT_OK;
+}
+}  // namespace
+
 extern "C" int hlhgat_adam_flat_prepared(float* param, const float* grad, float* exp_avg,
                                          float* exp_avg_sq, int64_t n, const float* step,
                                          double lr, double beta1, double beta2, double eps,
                                          double weight_decay, void* stream) {
   HLH_CHECK_ARG(n >= 0 && (n == 0 || (param && grad && exp_avg && exp_avg_sq)) && step,
                 "adam_flat_prepared: NULL pointer or n < 0");
-  if (n == 0) return HLHGAT_OK;
-  int64_t g = ceil_div(n, 256 * 2);
-  if (g > 2048) g = 2048;
-  AdamArgs a{param, grad, exp_avg, exp_avg_sq, n, const_cast<float*>(step), lr, beta1, beta2,
-             eps, weight_decay, 1};
-  launch(k_adam_flat, dim3((unsigned)g), dim3(256), 0, as_stream(stream), nullptr, a);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return adam_launch(param, grad, exp_avg, exp_avg_sq, n, const_cast<float*>(step), lr, nullptr,
+                     beta1, beta2, eps, weight_decay, 1, as_stream(stream));
 }
 
 extern "C" int hlhgat_adam_flat(float* param, const float* grad, float* exp_avg,
@@ -378,19 +405,32 @@ extern "C" int hlhgat_adam_flat(float* param, const float* grad, float* exp_avg,
                                 double weight_decay, void* stream) {
   HLH_CHECK_ARG(n >= 0 && (n == 0 || (param && grad && exp_avg && exp_avg_sq)) && step,
                 "adam_flat: NULL pointer or n < 0");
-  if (n == 0) {
-    launch(k_adam_step_inc, dim3(1), dim3(1), 0, as_stream(stream), nullptr, step);
-    HLH_CHECK_LAUNCH();
-    return HLHGAT_OK;
-  }
-  int64_t g = ceil_div(n, 256 * 2);
-  if (g > 2048) g = 2048;
-  AdamArgs a{param, grad, exp_avg, exp_avg_sq, n, step, lr, beta1, beta2, eps, weight_decay, 0};
-  launch(k_adam_flat, dim3((unsigned)g), dim3(256), 0, as_stream(stream), nullptr, a);
-  HLH_CHECK_LAUNCH();
-  launch(k_adam_step_inc, dim3(1), dim3(1), 0, as_stream(stream), nullptr, step);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return adam_launch(param, grad, exp_avg, exp_avg_sq, n, step, lr, nullptr, beta1, beta2, eps,
+                     weight_decay, 0, as_stream(stream));
+}
+
+extern "C" int hlhgat_adam_flat_dev_prepared(float* param, const float* grad, float* exp_avg,
+                                             float* exp_avg_sq, int64_t n, const float* step,
+                                             const double* lr_dev, double beta1, double beta2,
+                                             double eps, double weight_decay, void* stream) {
+  HLH_CHECK_ARG(n >= 0 && (n == 0 || (param && grad && exp_avg && exp_avg_sq)) && step,
+                "adam_flat_dev_prepared: NULL pointer or n < 0");
+  HLH_CHECK_ARG(lr_dev && aligned8(lr_dev),
+                "adam_flat_dev_prepared: lr_dev must be an 8-byte aligned device pointer");
+  return adam_launch(param, grad, exp_avg, exp_avg_sq, n, const_cast<float*>(step), 0.0, lr_dev,
+                     beta1, beta2, eps, weight_decay, 1, as_stream(stream));
+}
+
+extern "C" int hlhgat_adam_flat_dev(float* param, const float* grad, float* exp_avg,
+                                    float* exp_avg_sq, int64_t n, float* step,
+                                    const double* lr_dev, double beta1, double beta2, double eps,
+                                    double weight_decay, void* stream) {
+  HLH_CHECK_ARG(n >= 0 && (n == 0 || (param && grad && exp_avg && exp_avg_sq)) && step,
+                "adam_flat_dev: NULL pointer or n < 0");
+  HLH_CHECK_ARG(lr_dev && aligned8(lr_dev),
+                "adam_flat_dev: lr_dev must be an 8-byte aligned device pointer");
+  return adam_launch(param, grad, exp_avg, exp_avg_sq, n, step, 0.0, lr_dev, beta1, beta2, eps,
+                     weight_decay, 0, as_stream(stream));
 }
 
 // --- L1 loss (torch.nn.L1Loss, reduction "mean") ------------------------------

@@ -148,6 +148,13 @@ SIGNATURES = {
                                           c_f64, c_f64, c_f64, c_vp]),
     "hlhgat_adam_flat": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_f64, c_f64, c_f64,
                                  c_f64, c_f64, c_vp]),
+    "hlhgat_adam_flat_dev": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64, c_f64,
+                                     c_f64, c_f64, c_vp]),
+    "hlhgat_adam_flat_dev_prepared": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_f64,
+                                              c_f64, c_f64, c_f64, c_vp]),
+    "hlhgat_average_precision_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "hlhgat_average_precision": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                         c_vp, c_sz, c_vp]),
     "hlhgat_bce_logits_fwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "hlhgat_bce_logits_bwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_l1_loss_fwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -207,6 +214,7 @@ SIGMA_SIGMOID, SIGMA_RELU = 0, 1
 DEVERR_BN_STATE = 1
 DEVERR_HODGE_SIZE = 2
 DEVERR_LABEL = 4
+DEVERR_METRIC_LABEL = 8
 LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
 CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
 LOSS_ONE_LAUNCH_MAX = 16384  # up to here the loss forwards need no workspace

@@ -32,7 +32,7 @@ __all__ = [
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
-    "bce_logits_loss", "cross_entropy",
+    "bce_logits_loss", "cross_entropy", "average_precision",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -1647,6 +1647,22 @@ def dropout_manual_seed(seed: int, device=None) -> None:
     _dropout_st(device).set(int(seed) & _MASK64)
 
 
+def dropout_set_state(seed: int, step: int, device=None, site: int = 0) -> None:
+    """Restore a checkpointed (seed, step[, site]) as dropout_state returned
+    it (the seed already carries the rank offset): one host write and one
+    small copy, outside capture.  `site` is the host-side launch counter: an
+    eager step draws its masks at the next sites, so eager training resumes
+    on the uninterrupted run's masks only with it; a captured step keeps the
+    sites it was captured with."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("hlhgat: dropout_set_state during a graph capture")
+    st = _dropout_st(device)
+    s = int(seed) & _MASK64
+    s = s - (1 << 64) if s >= (1 << 63) else s
+    st.dev.copy_(torch.tensor([s, int(step)], dtype=torch.int64))
+    st.site = int(site) & 0xffffffff
+
+
 def dropout_set_rank(rank: int, device=None) -> None:
     """Data-parallel rank of this process (TrainStep, world > 1): the current
     and every later seed of `device` is offset by dropout_rank_seed."""
@@ -2247,11 +2263,15 @@ def adam_prepare(grad: torch.Tensor, step: torch.Tensor) -> None:
 
 
 def adam_flat(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor,
-              exp_avg_sq: torch.Tensor, step: torch.Tensor, lr: float, betas, eps: float,
+              exp_avg_sq: torch.Tensor, step: torch.Tensor, lr, betas, eps: float,
               weight_decay: float, prepared: bool = False) -> None:
     """One torch.optim.Adam (fused, capturable) update of a flat fp32 buffer;
     `step` the fp32 step count on device (incremented; prepared=True: already
-    incremented by adam_prepare)."""
+    incremented by adam_prepare).  `lr` is a Python float (a by-value kernel
+    argument: a captured launch keeps it) or a 0-dim / 1-element fp64 tensor
+    on the same device, read by the launch itself (hlhgat_adam_flat_dev*: a
+    captured launch follows later fills of the tensor).  Equal values give
+    equal bits either way."""
     for t, name in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"),
                     (exp_avg_sq, "exp_avg_sq"), (step, "step")):
         _req_dev(t, name)
@@ -2260,10 +2280,19 @@ def adam_flat(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor,
     n = param.numel()
     if not (grad.numel() == exp_avg.numel() == exp_avg_sq.numel() == n):
         raise RuntimeError("hlhgat: adam_flat: buffer sizes differ")
-    fn = LIB.hlhgat_adam_flat_prepared if prepared else LIB.hlhgat_adam_flat
+    hyper = (float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream(param))
+    if torch.is_tensor(lr):
+        _req_dev(lr, "lr", torch.float64)
+        if lr.numel() != 1 or lr.device != param.device:
+            raise RuntimeError(f"hlhgat: adam_flat: a tensor lr must be one fp64 value on "
+                               f"{param.device} (got {tuple(lr.shape)} on {lr.device})")
+        fn = LIB.hlhgat_adam_flat_dev_prepared if prepared else LIB.hlhgat_adam_flat_dev
+        lr_arg = lr.data_ptr()
+    else:
+        fn = LIB.hlhgat_adam_flat_prepared if prepared else LIB.hlhgat_adam_flat
+        lr_arg = float(lr)
     check(fn(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-             step.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(eps),
-             float(weight_decay), _stream(param)), "adam_flat")
+             step.data_ptr(), lr_arg, *hyper), "adam_flat")
 
 
 class _L1LossFn(torch.autograd.Function):
@@ -2518,6 +2547,65 @@ def cross_entropy(input: torch.Tensor, label: torch.Tensor, *, ignore_index: int
 
 
 # ----------------------------------------------------------------------------
+# evaluation metrics (csrc/metrics.hip)
+# ----------------------------------------------------------------------------
+_AP_WS = {}  # (device, stream, n, C) -> workspace, at most _AP_WS_MAX (oldest out first)
+_AP_WS_MAX = 8
+
+
+def _ap_workspace(x: torch.Tensor, n: int, Cc: int) -> torch.Tensor:
+    """The sort workspace of average_precision.  Eager calls share one per
+    (device, stream, n, C) -- the epoch loop needs two, train and validation --
+    in a cache of at most _AP_WS_MAX entries, so a caller whose n varies from
+    call to call does not grow it without bound (a dropped workspace goes back
+    to torch's allocator in stream order).  Inside a graph capture the
+    workspace is a fresh torch.empty from the graph's own pool, which lives as
+    long as the graph and is never handed to an eager call."""
+    need = max(int(LIB.hlhgat_average_precision_workspace_bytes(n, Cc)), 256)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need, dtype=torch.uint8, device=x.device)
+    key = (x.device.index, _stream(x), n, Cc)
+    ws = _AP_WS.pop(key, None)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    _AP_WS[key] = ws  # most recently used last
+    while len(_AP_WS) > _AP_WS_MAX:
+        _AP_WS.pop(next(iter(_AP_WS)))
+    return ws
+
+
+def average_precision(pred: torch.Tensor, label: torch.Tensor):
+    """(ap [C] fp64, counts [C, 3] int32) on the device: per class (column)
+    scikit-learn's average_precision_score over the rows whose label is not
+    NaN, the per-class quantity of the reference's eval_ap
+    (lib/Hodge_Dataset.py:73-94); counts = labelled rows, labels == 1, labels
+    == 0.  A class without a 1 or without a 0, or with a non-finite score in a
+    labelled row, gets NaN.  Ties (equal fp32 scores, -0.0 == +0.0) form one
+    threshold.  A label that is neither NaN, 0 nor 1 counts as a negative and
+    raises the device error word.  pred / label: [n, C]; a column block of a
+    wider tensor (unit column stride) is read in place.  No host
+    synchronisation: the call captures into a hipGraph.  Not differentiable."""
+    _req_dev(pred, "pred")
+    if pred.dim() != 2 or pred.shape != label.shape or label.device != pred.device:
+        raise RuntimeError(f"hlhgat: average_precision wants pred and label [n, C] on one device, "
+                           f"got {tuple(pred.shape)} on {pred.device} and {tuple(label.shape)} on "
+                           f"{label.device}")
+    n, Cc = pred.shape
+    if n * Cc >= 2 ** 31 - 1:
+        raise RuntimeError(f"hlhgat: average_precision: n * C = {n * Cc} out of int32 range")
+    with torch.no_grad():
+        x = _rows2d(pred.detach(), "pred")
+        y = _rows2d(label.detach().to(torch.float32), "label")
+        ap = torch.empty(Cc, dtype=torch.float64, device=x.device)
+        counts = torch.empty((Cc, 3), dtype=torch.int32, device=x.device)
+        ws = _ap_workspace(x, n, Cc)
+        check(LIB.hlhgat_average_precision(x.data_ptr(), _ld(x), y.data_ptr(), _ld(y), n, Cc,
+                                           ap.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream(x)), "average_precision")
+    return ap, counts
+
+
+# ----------------------------------------------------------------------------
 # device error word (include/hlhgat.h: hlhgat_device_errors)
 # ----------------------------------------------------------------------------
 _DEVERR_TEXT = {
@@ -2527,6 +2615,8 @@ _DEVERR_TEXT = {
     _lib.DEVERR_LABEL: "cross_entropy (label bit): a label that is neither ignore_index nor "
                        "a class index in [0, C); its row was left out of the loss and the "
                        "gradient",
+    _lib.DEVERR_METRIC_LABEL: "average_precision: a label that is neither NaN, 0 nor 1; it was "
+                              "counted as a negative",
     _lib.DEVERR_BN_STATE: "BatchNorm: an arrival counter was found beyond its total (the "
                           "workspace was written by something else or shared by concurrent "
                           "launches); that launch's statistics are not trusted",

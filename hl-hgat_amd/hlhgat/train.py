@@ -266,7 +266,28 @@ class TrainStep:
     torch.optim.Adam).
 
     graphs=True replays a captured hipGraph per batch shape (requires a ROCm
-    device); graphs=False runs the same step eagerly (any device)."""
+    device); graphs=False runs the same step eagerly (any device).
+
+    Learning rate.  On a ROCm device with the HIP Adam (HIP_ADAM) the learning
+    rate is device state: one fp64 scalar, allocated here outside any
+    capture, that IS ``self.opt.param_groups[0]["lr"]``.  torch's schedulers
+    update a tensor lr in place, so an unmodified
+    ``torch.optim.lr_scheduler.*`` built on ``step.opt`` (the reference's
+    ReduceLROnPlateau) drives eager and replayed steps alike: the update
+    kernel reads the scalar itself, and one captured graph per batch shape
+    serves every learning rate.  ``set_lr`` fills it, ``lr`` reads it.  fp64,
+    not torch's fp32 tensor-lr convention, so a constant-lr run keeps the bits
+    it had with a by-value double.  On a CPU device ``opt.step()`` honours
+    ``param_groups`` as always.  With HIP_ADAM = False on a ROCm device
+    torch's fused Adam runs with a host float lr: eager steps follow
+    ``param_groups``, a captured step keeps the learning rate it was captured
+    with, and ``set_lr`` raises there when graphs are on.  Betas, eps and
+    weight decay are host constants fixed at construction.
+
+    Resume.  ``state_dict()`` / ``load_state_dict()`` carry the model, the
+    optimiser (moments, step count, learning rate) and the HIP dropout
+    counter; loading writes into the existing buffers, so captured graphs
+    stay valid."""
 
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, lr: float = 1e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -334,7 +355,10 @@ class TrainStep:
                 "step": torch.zeros((), dtype=torch.float32, device=dev),
                 "exp_avg": torch.zeros_like(self.flat),
                 "exp_avg_sq": torch.zeros_like(self.flat)}
-            self._hyper = (lr, betas, eps, weight_decay)
+            self._hyper = (betas, eps, weight_decay)
+            # the learning rate as device state (see the class docstring)
+            self._lr_dev = torch.full((), float(lr), dtype=torch.float64, device=dev)
+            self.opt.param_groups[0]["lr"] = self._lr_dev
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         # the gradient exchange runs (world > 1, or a one-rank group in the
         # tests' COLLECTIVES_AT_WORLD_1 mode)
@@ -587,7 +611,12 @@ class TrainStep:
             self.opt.step()
             return
         st = self.opt.state[self.master]
-        lr, betas, eps, wd = self._hyper
+        betas, eps, wd = self._hyper
+        lr = self.opt.param_groups[0]["lr"]
+        if lr is not self._lr_dev:
+            raise RuntimeError("TrainStep: opt.param_groups[0]['lr'] was replaced; the HIP Adam "
+                               "reads the device scalar made at construction (fill it in place: "
+                               "step.set_lr(value), or a torch lr_scheduler on step.opt)")
         ops.adam_flat(self.flat, self.flat_grad, st["exp_avg"], st["exp_avg_sq"], st["step"],
                       lr, betas, eps, wd, prepared=prepared)
 
@@ -917,8 +946,100 @@ class TrainStep:
             with self._stage_lock:
                 free[0].pending -= 1
 
+    # -- learning rate ------------------------------------------------------
+    def _capturing(self) -> bool:
+        return self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    @property
+    def lr(self) -> float:
+        """The current learning rate as a host float (synchronises when it is
+        device state)."""
+        return float(self.opt.param_groups[0]["lr"])
+
+    def set_lr(self, value: float) -> None:
+        """Set the learning rate of the following steps, replayed ones
+        included: an in-place fill of the device scalar on the current stream
+        (HIP Adam), or param_groups[0]["lr"] (CPU; eager torch Adam).  Refused
+        while a capture is open (the fill would become part of the graph), and
+        with torch's fused Adam under graphs=True, whose captured steps keep
+        their learning rate."""
+        if self._capturing():
+            raise RuntimeError("TrainStep.set_lr: a graph capture is open on the current stream")
+        if self._hip_adam:
+            self._lr_dev.fill_(float(value))
+            return
+        if self.graphs:
+            raise RuntimeError("TrainStep.set_lr: torch's fused Adam (HIP_ADAM = False) keeps the "
+                               "learning rate of its captured steps; use graphs=False or the HIP "
+                               "Adam")
+        self.opt.param_groups[0]["lr"] = float(value)
+
+    # -- checkpoints --------------------------------------------------------
     def state_dict(self):
-        return {"model": self.model.state_dict(), "opt": self.opt.state_dict()}
+        """{"model", "opt"} (+ "dropout": (seed, step) and "dropout_site", the
+        host-side launch counter, when the model has a live HIP Dropout; eager
+        steps resume on the uninterrupted run's masks, a step captured after
+        the resume draws equally valid masks at its own sites).  "opt" is the torch optimiser's state_dict: moments, step
+        count and, with the HIP Adam, the fp64 tensor learning rate."""
+        sd = {"model": self.model.state_dict(), "opt": self.opt.state_dict()}
+        if self._hip_adam:  # a snapshot, not the live scalar later fills would change
+            sd["opt"]["param_groups"][0]["lr"] = self._lr_dev.detach().clone()
+        if self._dropouts and ops.HIP_DROPOUT:
+            seed, step, site = ops.dropout_state(self.device)
+            sd["dropout"] = (seed, step)
+            sd["dropout_site"] = site
+        return sd
+
+    def load_state_dict(self, sd) -> None:
+        """Resume from state_dict(): parameters and buffers are copied into
+        the model (the parameters stay views of the flat buffer), the moments
+        and the step count into the optimiser state, the learning rate by fill
+        and the dropout counter by one small copy.  With the HIP Adam (and on
+        the CPU) nothing is reallocated, so graphs captured before the call
+        replay on the restored state.  With torch's fused Adam on a ROCm
+        device (HIP_ADAM = False) opt.load_state_dict replaces the state
+        tensors a captured step addresses: the call is refused there once a
+        graph has been captured (load before the first step).  A step
+        captured after a resume draws its dropout masks at the sites of that
+        capture: valid masks, not the uninterrupted run's (eager steps redraw
+        those exactly)."""
+        if self._capturing():
+            raise RuntimeError("TrainStep.load_state_dict: a graph capture is open")
+        if not self._hip_adam and self._graphs:
+            raise RuntimeError("TrainStep.load_state_dict: torch's fused Adam (HIP_ADAM = False) "
+                               "would replace the optimiser state the captured steps address; "
+                               "load before the first step, or use the HIP Adam")
+        ptrs = [p.data_ptr() for p in self.params]
+        self.model.load_state_dict(sd["model"])
+        if [p.data_ptr() for p in self.params] != ptrs:
+            raise RuntimeError("TrainStep.load_state_dict: a parameter left the flat buffer")
+        osd = sd["opt"]
+        if not self._hip_adam:
+            self.opt.load_state_dict(osd)
+        else:
+            groups, states = osd["param_groups"], osd["state"]
+            if len(groups) != 1 or len(groups[0]["params"]) != 1:
+                raise ValueError("TrainStep.load_state_dict: expected one parameter group holding "
+                                 "the flat master parameter")
+            st = self.opt.state[self.master]
+            src = states.get(groups[0]["params"][0])
+            with torch.no_grad():
+                if src is None:  # saved before the first step
+                    for k in ("step", "exp_avg", "exp_avg_sq"):
+                        st[k].zero_()
+                else:
+                    if src["exp_avg"].numel() != self.flat.numel():
+                        raise ValueError(
+                            f"TrainStep.load_state_dict: checkpoint has "
+                            f"{src['exp_avg'].numel()} parameters, the model {self.flat.numel()}")
+                    for k in ("step", "exp_avg", "exp_avg_sq"):
+                        st[k].copy_(torch.as_tensor(src[k]).reshape(st[k].shape))
+                self._lr_dev.fill_(float(groups[0]["lr"]))
+            if "initial_lr" in groups[0]:  # left by a scheduler; its own state is the caller's
+                self.opt.param_groups[0]["initial_lr"] = groups[0]["initial_lr"]
+        if "dropout" in sd and self._dropouts:
+            seed, step = sd["dropout"]
+            ops.dropout_set_state(seed, step, self.device, site=sd.get("dropout_site", 0))
 
 
 class InferStep:

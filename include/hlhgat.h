@@ -814,6 +814,20 @@ int hlhgat_adam_flat_prepared(float* param, const float* grad, float* exp_avg,
                               float* exp_avg_sq, int64_t n, const float* step, double lr,
                               double beta1, double beta2, double eps, double weight_decay,
                               void* stream);
+/* The two entries above with the learning rate as device state: lr_dev points
+ * to ONE fp64 value on the device (8-byte aligned), read by the update's own
+ * launch (no extra launch), so a launch captured into a hipGraph follows a
+ * scheduler that rewrites the value between replays.  fp64, not torch's fp32
+ * tensor-lr convention: the arithmetic is the by-value entries' on the same
+ * double, so *lr_dev == lr gives the same bits (float(1e-3) promoted to double
+ * is not 1e-3).  Betas, eps and weight decay stay by-value constants. */
+int hlhgat_adam_flat_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                         int64_t n, float* step, const double* lr_dev, double beta1,
+                         double beta2, double eps, double weight_decay, void* stream);
+int hlhgat_adam_flat_dev_prepared(float* param, const float* grad, float* exp_avg,
+                                  float* exp_avg_sq, int64_t n, const float* step,
+                                  const double* lr_dev, double beta1, double beta2, double eps,
+                                  double weight_decay, void* stream);
 
 /* L1 loss, torch.nn.L1Loss(reduction="mean") of the ZINC training loop
  * (torch's sub / abs / mean and its five backward launches):
@@ -913,6 +927,38 @@ int hlhgat_cross_entropy_bwd(const float* x, int64_t ldx, int64_t rows, int64_t 
                              const int64_t* stats, const float* gout, float* dx, int64_t lddx,
                              void* stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip) -------------------------------- */
+/* Average precision per class, the reference's eval_ap
+ * (lib/Hodge_Dataset.py:73-94: scikit-learn's average_precision_score per
+ * column over the rows whose label is not NaN) without the host round trip.
+ * pred [n, C] fp32 scores (row stride ldp >= C), label [n, C] fp32 (row
+ * stride ldl >= C; NaN = unlabelled).  Per class c:
+ *   the rows with a NaN label are dropped; the m others are sorted by score,
+ *   descending; rows with equal scores (-0.0 == +0.0) form one threshold
+ *   group; tp_k = positives (label == 1) up to the end of group k, r_k = the
+ *   1-based index of its last row, P = all positives;
+ *   ap[c] = sum_k ((tp_k - tp_{k-1}) / P) * (tp_k / r_k)  in fp64;
+ *   counts[c] = {labelled rows m, labels == 1, labels == 0} (int32);
+ *   the class is valid iff it has a label == 1 and a label == 0; an invalid
+ *   class, or one with a non-finite score in a labelled row (scikit-learn
+ *   raises), gets ap[c] = NaN.
+ * A non-NaN label other than 0 or 1 counts as a negative (in neither the
+ * positives nor the zeros) and raises HLHGAT_DEVERR_METRIC_LABEL.
+ * Two launches around one hipcub radix sort of n*C 64-bit keys (class |
+ * unlabelled bit | order-preserving image of the score) with a one-byte
+ * value: the keys, the sort, then one workgroup per class walks its sorted
+ * segment.  No
+ * floating-point atomics, a fixed summation order (each thread adds the terms
+ * of its rows in row order, then one fixed tree): a function of the inputs,
+ * bitwise equal across runs, eager or replayed.  No host synchronisation and
+ * no allocation (temporary storage is `workspace`, at least
+ * hlhgat_average_precision_workspace_bytes(n, C) bytes, 256-byte aligned), so
+ * the call captures into a hipGraph.  n * C < 2^31. */
+size_t hlhgat_average_precision_workspace_bytes(int64_t n, int64_t C);
+int hlhgat_average_precision(const float* pred, int64_t ldp, const float* label, int64_t ldl,
+                             int64_t n, int64_t C, double* ap, int32_t* counts,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- workspaces --------------------------------------------------------- */
 /* Zero `bytes` (a multiple of 4) at p with a kernel on `stream` (graph-capture
  * safe; used to initialise the BatchNorm workspace counters). */
@@ -943,6 +989,9 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
 /* hlhgat_cross_entropy_fwd: a label that is neither ignore_index nor a class
  * index; its row was left out of the loss and the gradient */
 #define HLHGAT_DEVERR_LABEL 4u
+/* hlhgat_average_precision: a label that is neither NaN, 0 nor 1; its row was
+ * counted as a negative */
+#define HLHGAT_DEVERR_METRIC_LABEL 8u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 
