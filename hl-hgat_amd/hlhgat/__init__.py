@@ -11,7 +11,8 @@ from . import ops  # noqa: F401,E402  (loads libhlhgat.so; raises if missing)
 from .hodge_cheb_conv import (HL_filter, HodgeChebConv, HodgeLaguerreConv,  # noqa: F401,E402
                               HodgeLaguerreFastConv, Inception1D, MSI, NodeEdgeInt, SAPool)
 from .hodge_dataset import (Batch, BoundaryOperator, PairData, adj2par1, collate,  # noqa: F401,E402
-                            degree)
+                            degree, fc2mask)
+from .pipeline import BrainPipeline, brain_target  # noqa: F401,E402
 from .hodge_st_model import (HL_HGAT_attpool, HL_HGCNN_CIFAR10SP_dense_int3_attpool,  # noqa: F401,E402
                              HL_HGCNN_CIFAR10SP_dense_int3_pyr, HL_HGCNN_pepfunc_dense_int3_pyr,
                              HL_HGCNN_TSP_dense_int3_pyr, HL_HGCNN_zinc_dense_int3_attpool,

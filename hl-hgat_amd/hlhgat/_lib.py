@@ -206,6 +206,12 @@ SIGNATURES = {
     "hlhgat_time_readout_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_time_readout_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp,
                                         c_vp]),
+    "hlhgat_fc_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "hlhgat_fc_prepare": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                  c_sz, c_vp]),
+    "hlhgat_fc_dense": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "hlhgat_fc_edges": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                c_i64, c_vp]),
 }
 
 # constants from include/hlhgat.h

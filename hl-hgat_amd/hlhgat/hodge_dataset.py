@@ -24,7 +24,7 @@ import torch
 __all__ = ["PairData", "Batch", "collate", "adj2par1", "BoundaryOperator", "degree",
            "hodge_laplacians", "dense_to_sparse", "is_sorted_symmetric", "locality_order",
            "static_caps", "pad_batch", "level_caps", "pad_levels", "PackedGraphs", "halo_tiles", "graclus", "mlgc", "mlgc_weighted", "mlgc_map", "to_undirected_mean",
-           "hodge_factor_ok", "hodge_coo_from_boundary"]
+           "hodge_factor_ok", "hodge_coo_from_boundary", "fc2mask"]
 
 _INC_KEYS = ("edge_index_s", "edge_index_t", "edge_index", "row_order_s", "row_order_t")
 _HODGE_KEYS = ("edge_index_s", "edge_index_t")
@@ -1294,3 +1294,43 @@ def mlgc_weighted(g: "PairData", seed: int = 0):
     c_node, c_edge, ei1, n1 = mlgc_map(lab, np.asarray(g.edge_index))
     return (_mlgc_level(ei1, n1), torch.from_numpy(c_node.astype(np.float32)).view(-1, 1),
             torch.from_numpy(c_edge).view(-1, 1))
+
+
+def fc2mask(FC: torch.Tensor, threshmode: int = 1, k_ratio: float = 0.25) -> torch.Tensor:
+    """FC2mask (HL-HGAT-DEMO/lib/Hodge_Dataset.py:148-178): the group-level
+    skeleton mask from a cohort's FC stack [S, N, N], as tensor ops on FC's
+    device (ops.fc_dense builds the stack there).  Same arguments and result:
+    threshmode 1 keeps the pairs whose |mean FC| is strictly above the
+    int(k_ratio N^2)-th largest positive value, 2 those whose std / |mean| is
+    strictly below the k-th smallest positive value (both int64), anything
+    else the published per-region rule, symmetrised (float; see the comment
+    in the body); the upper triangle triu(1) is returned.  The reference's boolean indexing
+    mean_FC[mean_FC > 0] (a host sync on a device) is a masked top-k here: the
+    k-th value is the same."""
+    num_rois = FC.shape[1]
+    mean_FC = FC.mean(dim=0).abs()
+    k = int(k_ratio * num_rois ** 2)
+    if threshmode == 1:
+        cand = torch.where(mean_FC > 0, mean_FC, torch.full_like(mean_FC, float("-inf")))
+        v = cand.reshape(-1).topk(k=k)[0]
+        mask = (mean_FC > v[-1]).to(torch.long)
+    elif threshmode == 2:
+        mean_FC = FC.std(dim=0) / mean_FC
+        cand = torch.where(mean_FC > 0, mean_FC, torch.full_like(mean_FC, float("inf")))
+        v = cand.reshape(-1).topk(k=k, largest=False)[0]
+        mask = (mean_FC < v[-1]).to(torch.long)
+    else:
+        # The reference's loop (:172-175) rebinds its row variable i to topk's
+        # INDICES, so row r's k-th value thresholds the k rows topk picked, not
+        # row r, and a later r overwrites an earlier one.  Reproduced as
+        # published: row j is compared with the k-th value of the LAST row r
+        # whose top k contains j, and stays 0 if no row's does.
+        v, idx = mean_FC.topk(k=int(num_rois * k_ratio), dim=1)
+        r = torch.arange(num_rois, device=FC.device).view(-1, 1).expand_as(idx)
+        last = torch.full((num_rois,), -1, dtype=torch.long, device=FC.device)
+        last.scatter_reduce_(0, idx.reshape(-1), r.reshape(-1), "amax")
+        thr = v[:, -1][last.clamp(min=0)].view(-1, 1)
+        mask = ((mean_FC > thr) & (last >= 0).view(-1, 1)).to(torch.float)
+        mask = mask + mask.T
+        mask[mask == 2] = 1
+    return mask.triu(1)

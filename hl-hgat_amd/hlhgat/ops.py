@@ -33,6 +33,7 @@ __all__ = [
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
     "bce_logits_loss", "cross_entropy", "average_precision",
+    "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -2603,6 +2604,172 @@ def average_precision(pred: torch.Tensor, label: torch.Tensor):
                                            ap.data_ptr(), counts.data_ptr(), ws.data_ptr(),
                                            ws.numel(), _stream(x)), "average_precision")
     return ap, counts
+
+
+# ----------------------------------------------------------------------------
+# brain input: z-scored series and functional connectivity (csrc/fc.hip)
+# ----------------------------------------------------------------------------
+FC_TILE = 64  # the correlation kernel's tile edge (csrc/fc.hip)
+
+
+@dataclass
+class FcPrepared:
+    """What fc_prepare leaves for fc_dense / fc_edges: the workspace with the
+    centred unit-norm rows, the shape it was prepared for and, if wanted, z."""
+    workspace: torch.Tensor
+    n_graphs: int
+    n_nodes: int
+    T: int
+    z: Optional[torch.Tensor]
+
+
+def fc_prepare(x: torch.Tensor, n_graphs: int, window=None, want_z: bool = True, *,
+               n_nodes: Optional[int] = None, graph_rows: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None,
+               z: Optional[torch.Tensor] = None) -> FcPrepared:
+    """The row pass of Brain_MLGC_ALL.get for n_graphs subjects at once
+    (HL-HGAT-DEMO/lib/Hodge_Dataset.py:136): x is [n_graphs * N, T_all] (rows
+    may be strided), graph g owning rows [g N, (g + 1) N); window = (t0, T)
+    selects columns [t0, t0 + T) (None: all).  Returns an FcPrepared whose z
+    ([n_graphs * N, T], want_z) is (x - mean_g) / std_g with the graph's mean
+    and unbiased std over its window, and whose workspace feeds fc_dense /
+    fc_edges.  graph_rows (int64 [n_graphs], device) with n_nodes = N instead
+    picks graph g's rows from row graph_rows[g] of a larger x; its values are
+    the caller's to bound.  workspace: a uint8 tensor of at least
+    hlhgat_fc_workspace_bytes to reuse; z: a contiguous [n_graphs * N, T]
+    tensor to fill (want_z).  Not differentiable: these are inputs."""
+    _req_dev(x, "x")
+    if x.dim() != 2:
+        raise RuntimeError(f"hlhgat: fc_prepare wants x [rows, T], got {tuple(x.shape)}")
+    x = _rows2d(x.detach(), "x")
+    G = int(n_graphs)
+    if graph_rows is None:
+        if G < 0 or (G > 0 and x.size(0) % G) or (G == 0 and x.size(0)):
+            raise RuntimeError(f"hlhgat: fc_prepare: {x.size(0)} rows do not split into "
+                               f"{G} graphs")
+        N = x.size(0) // G if G else (int(n_nodes) if n_nodes else 1)
+        if n_nodes is not None and G and int(n_nodes) != N:
+            raise RuntimeError(f"hlhgat: fc_prepare: n_nodes={n_nodes} but x has {N} rows per graph")
+    else:
+        if n_nodes is None:
+            raise RuntimeError("hlhgat: fc_prepare: graph_rows needs n_nodes")
+        _req_dev(graph_rows, "graph_rows", torch.int64)
+        N = int(n_nodes)
+        if graph_rows.numel() != G or not graph_rows.is_contiguous() or N > x.size(0):
+            raise RuntimeError(f"hlhgat: fc_prepare: graph_rows must be contiguous int64 [{G}] and "
+                               f"n_nodes <= {x.size(0)} rows")
+    t0, T = (0, x.size(1)) if window is None else (int(window[0]), int(window[1]))
+    if t0 < 0 or t0 + T > x.size(1):
+        raise RuntimeError(f"hlhgat: fc_prepare: window [{t0}, {t0 + T}) outside the {x.size(1)} "
+                           f"columns of x")
+    need = max(int(LIB.hlhgat_fc_workspace_bytes(G, N, T)), 16)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    elif workspace.device != x.device or workspace.dtype != torch.uint8 or \
+            not workspace.is_contiguous() or workspace.numel() < need:
+        raise RuntimeError(f"hlhgat: fc_prepare: workspace must be contiguous uint8 [>= {need}] on "
+                           f"{x.device}")
+    if not want_z:
+        z = None
+    elif z is None:
+        z = torch.empty((G * N, T), dtype=torch.float32, device=x.device)
+    else:
+        _req_dev(z, "z")
+        if tuple(z.shape) != (G * N, T) or not z.is_contiguous() or z.device != x.device:
+            raise RuntimeError(f"hlhgat: fc_prepare: z must be contiguous [{G * N}, {T}] on "
+                               f"{x.device}")
+    check(LIB.hlhgat_fc_prepare(x.data_ptr(), _ld(x), _ptr(graph_rows), G, N, t0, T, _ptr(z),
+                                workspace.data_ptr(), workspace.numel(), _stream(x)),
+          "fc_prepare")
+    return FcPrepared(workspace, G, N, T, z)
+
+
+def fc_dense(prep: FcPrepared, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fc [G, N, N]: torch.corrcoef of every prepared graph (the FC stack that
+    FC2mask thresholds, lib/Hodge_Dataset.py:148-153): exactly symmetric,
+    clamped to [-1, 1], NaN on the row, column and diagonal entry of a region
+    whose series is constant over the window."""
+    G, N = prep.n_graphs, prep.n_nodes
+    ws = prep.workspace
+    if out is None:
+        out = torch.empty((G, N, N), dtype=torch.float32, device=ws.device)
+    else:
+        _req_dev(out, "out")
+        if tuple(out.shape) != (G, N, N) or not out.is_contiguous() or out.device != ws.device:
+            raise RuntimeError(f"hlhgat: fc_dense: out must be contiguous [{G}, {N}, {N}] on "
+                               f"{ws.device}")
+    check(LIB.hlhgat_fc_dense(ws.data_ptr(), G, N, prep.T, out.data_ptr(), _stream(ws)),
+          "fc_dense")
+    return out
+
+
+def fc_pair_table(edge_index, n: int):
+    """Host tables of one skeleton for fc_edges: (pair2edge, tiles), CPU
+    tensors.  pair2edge is int32 [n * n], -1 or the id of edge (i, j) at
+    i * n + j; tiles is int32 [n_tiles, 2], the (row tile, column tile) pairs
+    of FC_TILE-sized tiles that hold an edge.  edge_index is [2, E] with
+    i < j (the skeleton's triu(1).to_sparse().indices()); i >= j, an index
+    outside [0, n) and duplicate pairs raise."""
+    import numpy as np
+    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index,
+                    dtype=np.int64)
+    n = int(n)
+    if ei.ndim != 2 or ei.shape[0] != 2:
+        raise ValueError(f"fc_pair_table: edge_index must be [2, E], got {ei.shape}")
+    if n <= 0 or n * n >= 2 ** 31:
+        raise ValueError(f"fc_pair_table: n = {n} out of range")
+    i, j = ei[0], ei[1]
+    if ei.shape[1] and (i.min() < 0 or j.max() >= n):
+        raise ValueError(f"fc_pair_table: node index outside [0, {n})")
+    if (i >= j).any():
+        raise ValueError("fc_pair_table: every edge must have i < j")
+    key = i * n + j
+    if np.unique(key).size != key.size:
+        raise ValueError("fc_pair_table: duplicate pairs")
+    table = np.full(n * n, -1, dtype=np.int32)
+    table[key] = np.arange(key.size, dtype=np.int32)
+    nt = (n + FC_TILE - 1) // FC_TILE
+    tk = np.unique((i // FC_TILE) * nt + j // FC_TILE)
+    tiles = np.stack([tk // nt, tk % nt], 1).astype(np.int32).reshape(-1, 2)
+    return torch.from_numpy(table), torch.from_numpy(np.ascontiguousarray(tiles))
+
+
+def fc_edges(prep: FcPrepared, pair2edge: torch.Tensor, n_edges: int,
+             out: Optional[torch.Tensor] = None, tiles: Optional[torch.Tensor] = None
+             ) -> torch.Tensor:
+    """x_s of Brain_MLGC_ALL.get (lib/Hodge_Dataset.py:137, :142): the
+    correlations at the skeleton's pairs only, [G * n_edges, 1], bit for bit
+    the entries of fc_dense; the dense stack is never formed.  pair2edge /
+    tiles: fc_pair_table's tables on the device (tiles None: every tile pair
+    of the upper triangle).  out: a [G * n_edges, 1] tensor to fill, which may
+    be one column of a wider slab (rows strided); rows of no edge keep their
+    content."""
+    G, N, E = prep.n_graphs, prep.n_nodes, int(n_edges)
+    ws = prep.workspace
+    _req_dev(pair2edge, "pair2edge", torch.int32)
+    if pair2edge.numel() != N * N or not pair2edge.is_contiguous() or pair2edge.device != ws.device:
+        raise RuntimeError(f"hlhgat: fc_edges: pair2edge must be contiguous int32 [{N * N}] on "
+                           f"{ws.device}")
+    if tiles is None:
+        nt = (N + FC_TILE - 1) // FC_TILE
+        tiles = torch.tensor([[r, c] for r in range(nt) for c in range(r, nt)],
+                             dtype=torch.int32).to(ws.device)
+    _req_dev(tiles, "tiles", torch.int32)
+    if tiles.dim() != 2 or tiles.size(1) != 2 or not tiles.is_contiguous() or \
+            tiles.device != ws.device:
+        raise RuntimeError("hlhgat: fc_edges: tiles must be contiguous int32 [n_tiles, 2]")
+    if out is None:
+        out = torch.empty((G * E, 1), dtype=torch.float32, device=ws.device)
+    else:
+        _req_dev(out, "out")
+        if out.dim() != 2 or tuple(out.shape) != (G * E, 1) or out.device != ws.device or \
+                (out.size(0) > 1 and out.stride(0) < 1):
+            raise RuntimeError(f"hlhgat: fc_edges: out must be [{G * E}, 1] on {ws.device}")
+    ld = out.stride(0) if out.size(0) > 1 else 1
+    check(LIB.hlhgat_fc_edges(ws.data_ptr(), G, N, prep.T, pair2edge.data_ptr(), E,
+                              tiles.data_ptr(), tiles.size(0), out.data_ptr(), ld, _stream(ws)),
+          "fc_edges")
+    return out
 
 
 # ----------------------------------------------------------------------------

@@ -39,6 +39,10 @@ lambda_max (fp64 Lanczos vs float32 eigh) within 1e-6 relative, so the
 Laplacian entries are; PE columns equal the reference's up to sign (the reference flips them at
 random, and an eigenvector's sign is arbitrary), checked where the
 eigenvalue is separated from its neighbours.
+
+BrainPipeline (below) is the DEMO brain model's input in the same spirit:
+Brain_MLGC_ALL.get's z-score and skeleton correlations for a whole batch on
+the device (csrc/fc.hip), the level list collated once per batch size.
 """
 from __future__ import annotations
 
@@ -50,7 +54,8 @@ import torch
 from .hodge_dataset import (Batch, PairData, _h2d, collate, dense_to_sparse, graclus,
                             hodge_laplacians, mlgc_batch, mlgc_batch_flat, mlgc_map)
 
-__all__ = ["SuperpixelPipeline", "to_undirected_min", "superpixel_raw"]
+__all__ = ["SuperpixelPipeline", "to_undirected_min", "superpixel_raw", "BrainPipeline",
+           "brain_target"]
 
 
 def to_undirected_min(edge_index, attr, n: int):
@@ -395,3 +400,192 @@ class SuperpixelPipeline:
             ops.set_hodge_factor(lv0.edge_index_s, lv0.edge_index, lv0.num_nodes)
             lv0.l1_factor = True
         return lv0, lv1
+
+
+def brain_target(scores, y_mean: float = 95.1377, y_std: float = 7.3) -> torch.Tensor:
+    """The regression target of Brain_MLGC_ALL.get (HL-HGAT-DEMO/lib/
+    Hodge_Dataset.py:140): (mean of the subject's first five scores, as
+    float32, - y_mean) / y_std, a 0-d float32 tensor."""
+    m = torch.tensor(np.asarray(scores)[:5].mean()).to(torch.float)
+    return (m - y_mean) / y_std
+
+
+class BrainPipeline:
+    """The DEMO brain model's input (HL-HGAT-DEMO/lib/Hodge_Dataset.py:130-145,
+    Brain_MLGC_ALL.get, and the DataLoader collation of OHBM_DEMO.ipynb) for
+    whole batches, on the device.
+
+    The reference z-scores each subject's [N, T] fMRI block by its global mean
+    and std (x_t), takes torch.corrcoef of it at the skeleton's edges (x_s),
+    deep-copies the whole level list per sample and lets the DataLoader
+    concatenate the copies.  The skeleton and its Laplacians are the same for
+    every subject, so here the level list is collated ONCE per batch size
+    (hodge_dataset.collate: CSR, incidence and factor tables included), moved
+    to the device and cached; batch() returns it with only x_t, x_s and y of
+    level 0 replaced -- two library calls (ops.fc_prepare, ops.fc_edges) and
+    one gather, no host synchronisation, no copy of graph structure and no
+    allocation but the three outputs and the batch's index upload.
+
+    series: S arrays [N, T_s] (equal N).  resident=True uploads them once as
+      one [S, N, Tmax] block; resident=False keeps that block pinned on the
+      host and uploads only a batch's rows.
+    targets: [S] floats (brain_target).
+    levels: the per-subject level list [fine, coarse, ...] of PairData, level
+      p carrying pos_t / pos_s, as the notebook builds it once; the fine
+      level's edge_index ([2, E], i < j) is the skeleton.
+
+    Two stated differences from the reference:
+      * window="random" draws t_begin in [0, 75) and a length in [250, 300)
+        ONCE PER BATCH from `seed`; the reference draws them per sample
+        (:131-133), which its own collation cannot batch when the lengths
+        differ (x_t rows of different widths);
+      * a region whose series is constant over the window gets NaN on its
+        edges (the exact 0 / 0); the reference's float result there is
+        rounding noise.
+    device="cpu" restates the reference's arithmetic in torch, sample by
+    sample ((f - f.mean()) / f.std(), torch.corrcoef, the indexing): the
+    restatement the golden test pins (tests/golden/make_golden_brainfc.py).
+    The device path works on the current stream and reuses one workspace per
+    batch size: use a batch's tensors (or order later work after them on that
+    stream) before asking for the next batch from another stream."""
+
+    def __init__(self, series: Sequence, targets, levels: Sequence[PairData],
+                 resident: bool = True):
+        if len(series) == 0:
+            raise ValueError("BrainPipeline: no series")
+        # as the reference reads a sample: torch.tensor(arr).to(torch.float)
+        self.series = [torch.as_tensor(np.asarray(s)).to(torch.float) for s in series]
+        self.N = int(self.series[0].shape[0])
+        if any(s.dim() != 2 or s.shape[0] != self.N for s in self.series):
+            raise ValueError("BrainPipeline: every series must be [N, T] with the same N")
+        self.lens = np.array([int(s.shape[1]) for s in self.series], dtype=np.int64)
+        self.targets = torch.as_tensor(np.asarray(targets, dtype=np.float32)).reshape(-1)
+        if self.targets.numel() != len(self.series):
+            raise ValueError("BrainPipeline: one target per series")
+        self.levels = list(levels)
+        fine = self.levels[0]
+        self.edge_index = torch.as_tensor(np.asarray(fine.edge_index)).to(torch.int64)
+        self.E = int(self.edge_index.shape[1])
+        nf = fine.x_t.shape[0] if torch.is_tensor(getattr(fine, "x_t", None)) else self.N
+        if int(nf) != self.N:
+            raise ValueError(f"BrainPipeline: the fine level has {nf} nodes, the series {self.N}")
+        from . import ops
+        self._pair2edge, self._tiles = ops.fc_pair_table(self.edge_index, self.N)
+        self.resident = bool(resident)
+        self._block = None   # [S, N, Tmax] host block (pinned when it feeds a device)
+        self._dev = {}       # device -> per-device state
+        self._levels = {}    # (device, B) -> collated level list
+
+    def __len__(self) -> int:
+        return len(self.series)
+
+    # -- cached state ----------------------------------------------------------
+    def _host_block(self, pin: bool) -> torch.Tensor:
+        if self._block is None:
+            blk = torch.zeros((len(self.series), self.N, int(self.lens.max())),
+                              dtype=torch.float32)
+            for i, s in enumerate(self.series):
+                blk[i, :, :s.shape[1]] = s
+            self._block = blk.pin_memory() if pin else blk
+        return self._block
+
+    def _device_state(self, dev: torch.device) -> dict:
+        st = self._dev.get(dev)
+        if st is None:
+            blk = self._host_block(pin=True)
+            st = {"pair2edge": self._pair2edge.to(dev), "tiles": self._tiles.to(dev),
+                  "targets": self.targets.to(dev), "ws": {}, "stage": {}}
+            if self.resident:
+                st["block"] = blk.to(dev).view(-1, blk.shape[2])
+            self._dev[dev] = st
+        return st
+
+    def levels_for(self, B: int, device="cuda") -> List[Batch]:
+        """B copies of every level, collated once and cached per (device, B)."""
+        dev = torch.device(device)
+        key = (dev, int(B))
+        out = self._levels.get(key)
+        if out is None:
+            out = []
+            for p, lv in enumerate(self.levels):
+                g = lv
+                if p == 0:  # the placeholders that batch() replaces
+                    g = PairData(**{k: getattr(lv, k) for k in lv.keys()})
+                    g.x_t = torch.zeros(self.N, 1)
+                    g.x_s = torch.zeros(self.E, 1)
+                    g.y = None
+                b = collate([g] * int(B), check_hodge=True)
+                out.append(b.to(dev) if dev.type == "cuda" else b)
+            self._levels[key] = out
+        return out
+
+    def _window(self, idx, window, seed):
+        lens = self.lens[idx]
+        if window is None:
+            if (lens != lens[0]).any():
+                raise ValueError("BrainPipeline: window=None needs series of one length in a "
+                                 f"batch, got {sorted(set(lens.tolist()))}")
+            return 0, int(lens[0])
+        if isinstance(window, str):
+            if window != "random":
+                raise ValueError(f"BrainPipeline: window={window!r}")
+            rng = np.random.default_rng(seed)
+            t0 = int(rng.integers(0, 75))
+            T = int(rng.integers(250, 300))
+            T = min(T, int(lens.min()) - t0)  # a slice past the end is cut, as in the reference
+        else:
+            t0, T = int(window[0]), int(window[1])
+        if t0 < 0 or T < 2 or t0 + T > int(lens.min()):
+            raise ValueError(f"BrainPipeline: window [{t0}, {t0 + T}) does not fit series of "
+                             f"length {int(lens.min())} with at least two samples")
+        return t0, T
+
+    # -- the batch -------------------------------------------------------------
+    def batch(self, idx, window=None, seed: int = 0, device="cuda") -> List[Batch]:
+        """The level list of subjects idx: the cached collation of len(idx)
+        copies with x_t [B N, T], x_s [B E, 1] and y [B] of level 0 set.
+        window: None (the whole series), (t0, T), or "random" (see the class
+        docstring: one draw per batch)."""
+        import copy
+        idx = np.asarray([int(i) for i in idx], dtype=np.int64)
+        B = idx.size
+        if B == 0 or idx.min() < 0 or idx.max() >= len(self.series):
+            raise ValueError(f"BrainPipeline: subjects {idx.tolist()} outside [0, {len(self)})")
+        t0, T = self._window(idx, window, seed)
+        dev = torch.device(device)
+        levels = self.levels_for(B, dev)
+        lv0 = copy.copy(levels[0])  # the same structure tensors, three fields of its own
+        if dev.type == "cpu":
+            xs_t, xs_s = [], []
+            ei = self.edge_index
+            for i in idx:
+                f = self.series[i][:, t0:t0 + T]
+                f = (f - f.mean()) / f.std()
+                xs_t.append(f)
+                xs_s.append(torch.corrcoef(f)[ei[0], ei[1]].view(-1, 1))
+            lv0.x_t, lv0.x_s = torch.cat(xs_t), torch.cat(xs_s)
+            lv0.y = self.targets[torch.from_numpy(idx)]
+            return [lv0] + list(levels[1:])
+        from . import _lib, ops
+        st = self._device_state(dev)
+        ids = _h2d(np.concatenate([idx, idx * self.N]), dev)
+        if self.resident:
+            x, rows = st["block"], ids[B:]
+        else:  # the batch's rows only, from the pinned block into a reused buffer
+            blk = self._host_block(pin=True)
+            x = st["stage"].get(B)
+            if x is None:
+                x = st["stage"][B] = torch.empty((B * self.N, blk.shape[2]), device=dev)
+            for b, i in enumerate(idx):
+                x[b * self.N:(b + 1) * self.N].copy_(blk[i], non_blocking=True)
+            rows = None
+        ws = st["ws"].get(B)
+        if ws is None:
+            need = int(_lib.LIB.hlhgat_fc_workspace_bytes(B, self.N, int(self.lens.max())))
+            ws = st["ws"][B] = torch.empty(need, dtype=torch.uint8, device=dev)
+        prep = ops.fc_prepare(x, B, window=(t0, T), n_nodes=self.N, graph_rows=rows,
+                              workspace=ws)
+        lv0.x_t = prep.z
+        lv0.x_s = ops.fc_edges(prep, st["pair2edge"], self.E, tiles=st["tiles"])
+        lv0.y = st["targets"].index_select(0, ids[:B])
+        return [lv0] + list(levels[1:])

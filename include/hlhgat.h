@@ -1147,6 +1147,46 @@ int hlhgat_dropout_bwd(const float* dy, int64_t lddy, int64_t n, int64_t d, uint
 /* state[1] += 1 (one thread): the next step's masks.  Capturable. */
 int hlhgat_dropout_advance(int64_t* state, void* stream);
 
+/* ---- brain input: z-scored series and functional connectivity ----------- */
+/* The per-sample arithmetic of Brain_MLGC_ALL.get (HL-HGAT-DEMO/lib/
+ * Hodge_Dataset.py:130-145) and of the cohort loop that feeds FC2mask
+ * (:148-178; OHBM_DEMO.ipynb, FC[i] = torch.corrcoef(...)), for G graphs of N
+ * regions at once.  x holds the series as rows of pitch ldx; graph g owns the
+ * N rows from row graph_rows[g] (int64 [G], device) or, with graph_rows NULL,
+ * from row g * N; the window is columns [t0, t0 + T).
+ *
+ * Bytes of the workspace for G graphs (0 when G <= 0, N <= 0 or T < 2): the
+ * centred unit-norm rows at pitch roundup(T, 4) and two doubles per row. */
+size_t hlhgat_fc_workspace_bytes(int64_t G, int64_t N, int64_t T);
+/* The row pass (:136).  Per graph the mean and the UNBIASED std over its N * T
+ * window elements, z = (x - mean_g) / std_g written contiguously as [G*N, T]
+ * (z may be NULL: not wanted); per row the centred unit-norm row
+ * (x_i - mean_i) / ||x_i - mean_i|| into the workspace (16-byte aligned).
+ * Correlation is invariant to the graph's z-score, so the rows come from x
+ * directly.  A row that is constant over the window (min == max) becomes NaN:
+ * the exact-arithmetic 0 / 0 of the reference, whose own float result there is
+ * rounding noise.  fp64 accumulators in a fixed order: bitwise reproducible,
+ * and a graph's results do not depend on the other graphs of the call. */
+int hlhgat_fc_prepare(const float* x, int64_t ldx, const int64_t* graph_rows, int64_t G,
+                      int64_t N, int64_t t0, int64_t T, float* z, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* fc[G, N, N] = torch.corrcoef of every graph's window (:137 before the
+ * indexing; the FC stack of FC2mask, :148-153) from a prepared workspace:
+ * fp32 MFMA on 64 x 64 tiles with row tile <= column tile, each value stored
+ * at (i, j) and (j, i) (exactly symmetric), clamped to [-1, 1] as
+ * torch.corrcoef clamps; NaN stays NaN. */
+int hlhgat_fc_dense(const void* workspace, int64_t G, int64_t N, int64_t T, float* fc,
+                    void* stream);
+/* The skeleton's entries only (:137, corrcoef(...)[skeleton.indices()]):
+ * pair2edge is int32 [N * N], -1 or the edge id (< E) of the pair (i, j),
+ * i < j; tiles is int32 [n_tiles][2], the (row tile, column tile) pairs of
+ * 64 x 64 tiles that hold an edge.  The value of edge e of graph g goes to
+ * out[(g * E + e) * ld], bit for bit the dense entry; the dense stack is
+ * never written.  Entries of out that belong to no edge are left alone. */
+int hlhgat_fc_edges(const void* workspace, int64_t G, int64_t N, int64_t T,
+                    const int32_t* pair2edge, int64_t E, const int32_t* tiles, int64_t n_tiles,
+                    float* out, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@
 (b) one eager forward+backward of the checkpoint-shaped HL_HGAT_attpool on 5
     copies of tests/golden/brain_skeleton.npz, coarse level from
     hlhgat.hodge_dataset.mlgc_weighted.
+(d) the input side (hlhgat.pipeline.BrainPipeline, csrc/fc.hip) at B = 5,
+    N = 268, T = 375 on the same skeleton: a batch, the row pass and the two
+    correlation epilogues on their own, the dense epilogue on S = 50 subjects
+    as a fraction of the fp32 MFMA peak, and a torch-ops restatement on the
+    same device (per-subject torch.corrcoef plus the index).
 (c) last, in a child process with its own time limit: the same front end on
     torch's conv1d / max_pool1d (MIOpen), for the ratio -- or the note that it
     did not finish.
@@ -147,12 +152,12 @@ class _Level:
     pass
 
 
-def head(reps):
-    import hlhgat
+def skeleton_levels():
+    """[fine, coarse] on tests/golden/brain_skeleton.npz (coarse level from
+    hlhgat.hodge_dataset.mlgc_weighted) and the fine level's cluster maps."""
     from hlhgat.hodge_dataset import PairData, hodge_coo_from_boundary, mlgc_weighted
-    dev = torch.device("cuda:0")
     g = np.load(os.path.join(REPO, "tests", "golden", "brain_skeleton.npz"))
-    n, B = int(g["n_nodes"]), 5
+    n = int(g["n_nodes"])
     ei = torch.from_numpy(g["edge_index"].astype(np.int64))
     E = ei.shape[1]
     ei_t, w_t, ei_s, w_s = hodge_coo_from_boundary(g["edge_index"], n, float(g["lmax"]))
@@ -162,6 +167,16 @@ def head(reps):
                     edge_index=ei)
     fine.num_node1, fine.num_edge1 = n, E
     coarse, c_node, c_edge = mlgc_weighted(fine)
+    return fine, coarse, c_node, c_edge
+
+
+def head(reps):
+    import hlhgat
+    dev = torch.device("cuda:0")
+    B = 5
+    fine, coarse, c_node, c_edge = skeleton_levels()
+    n, E = int(fine.num_node1), int(fine.num_edge1)
+    ei_s = fine.edge_index_s
     n1, E1 = int(coarse.num_node1), int(coarse.num_edge1)
 
     def level(d, nn_, ne_, xt, xs):
@@ -197,6 +212,95 @@ def head(reps):
             "nnz_L1": int(ei_s.shape[1]), "fwd_bwd_ms": round(ms, 3)}
 
 
+def input_pipeline(reps):
+    """(d) the input side at B = 5, N = 268, T = 375 on the same skeleton:
+    BrainPipeline.batch (device time by events, host time per call without a
+    sync), the row pass and the two correlation epilogues on their own, the
+    dense epilogue on S = 50 subjects as a fraction of the fp32 MFMA peak, and
+    a torch-ops restatement on the same device (per subject (f - mean) / std,
+    torch.corrcoef, the index)."""
+    import hlhgat
+    from hlhgat import ops
+    dev = torch.device("cuda:0")
+    B, S = 5, 50
+    fine, coarse, c_node, c_edge = skeleton_levels()
+    fine.pos_t, fine.pos_s = c_node.view(-1), c_edge.view(-1)
+    n, E = int(fine.num_node1), int(fine.num_edge1)
+    rng = np.random.default_rng(0)
+    series = [((rng.standard_normal((n, 6)) @ rng.standard_normal((6, T))
+                + rng.standard_normal((n, T))) * 50 + 1000).astype(np.float32) for _ in range(S)]
+    pipe = hlhgat.BrainPipeline(series, np.zeros(S, np.float32), [fine, coarse])
+    t0 = time.perf_counter()
+    pipe.batch(range(B), device=dev)
+    torch.cuda.synchronize()
+    first_s = time.perf_counter() - t0  # collation of the level list, uploads
+    it = [0]
+
+    def one_batch():
+        k = it[0] = (it[0] + B) % S
+        return pipe.batch([(k + j) % S for j in range(B)], device=dev)
+
+    batch_ms = timed(one_batch, reps)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        one_batch()
+    host_ms = (time.perf_counter() - t0) * 1e3 / reps
+    torch.cuda.synchronize()
+
+    table, tiles = (t.to(dev) for t in ops.fc_pair_table(fine.edge_index, n))
+    block = torch.from_numpy(np.stack(series)).to(dev).view(S * n, T)
+    x5 = block[:B * n]
+    prep5 = ops.fc_prepare(x5, B)
+    ws5, z5 = prep5.workspace, prep5.z
+    out = torch.empty(B * E, 1, device=dev)
+    fc5 = torch.empty(B, n, n, device=dev)
+    res = {"graphs": B, "nodes": n, "T": T, "edges": E, "edge_tiles": int(tiles.shape[0]),
+           "first_batch_s": round(first_s, 3), "batch_ms": round(batch_ms, 4),
+           "batch_host_ms": round(host_ms, 4),
+           "prepare_ms": round(timed(lambda: ops.fc_prepare(x5, B, workspace=ws5, z=z5), reps), 4),
+           "prepare_no_z_ms": round(timed(lambda: ops.fc_prepare(x5, B, want_z=False,
+                                                                 workspace=ws5), reps), 4),
+           "edges_ms": round(timed(lambda: ops.fc_edges(prep5, table, E, out=out, tiles=tiles),
+                                   reps), 4),
+           "dense_ms": round(timed(lambda: ops.fc_dense(prep5, out=fc5), reps), 4)}
+    # the cohort-sized dense stack (FC2mask's input)
+    prep50 = ops.fc_prepare(block, S, want_z=False)
+    fc50 = torch.empty(S, n, n, device=dev)
+    ms50 = timed(lambda: ops.fc_dense(prep50, out=fc50), reps)
+    nt = -(-n // ops.FC_TILE)
+    tp = -(-T // 4) * 4
+    run_flops = 2.0 * S * (nt * (nt + 1) // 2) * ops.FC_TILE ** 2 * tp  # the tiles computed
+    alg_flops = 2.0 * S * n * n * T                                      # a full [N,T][T,N]
+    res["dense_S50"] = {"ms": round(ms50, 4), "gflop_full_product": round(alg_flops / 1e9, 3),
+                        "gflop_tiles_run": round(run_flops / 1e9, 3),
+                        "frac_mfma_peak_full_product": round(alg_flops / ms50 / 1e9 / PEAK_TF, 4),
+                        "frac_mfma_peak_tiles_run": round(run_flops / ms50 / 1e9 / PEAK_TF, 4)}
+    ei = fine.edge_index.to(dev)
+
+    def torch_batch():
+        xt, xs = [], []
+        for b in range(B):
+            f = block[b * n:(b + 1) * n]
+            f = (f - f.mean()) / f.std()
+            xt.append(f)
+            xs.append(torch.corrcoef(f)[ei[0], ei[1]].view(-1, 1))
+        return torch.cat(xt), torch.cat(xs)
+
+    def torch_dense():
+        return torch.stack([torch.corrcoef(block[i * n:(i + 1) * n]) for i in range(S)])
+
+    xt, xs = torch_batch()
+    res["torch_ops"] = {"batch_ms": round(timed(torch_batch, reps), 4),
+                        "dense_S50_ms": round(timed(torch_dense, reps), 4),
+                        "max_abs_diff_x_t": float((xt - z5).abs().max()),
+                        "max_abs_diff_x_s": float((xs - ops.fc_edges(prep5, table, E,
+                                                                     tiles=tiles)).abs().max())}
+    res["torch_ops"]["ratio_batch"] = round(res["torch_ops"]["batch_ms"] / batch_ms, 3)
+    res["torch_ops"]["ratio_dense_S50"] = round(res["torch_ops"]["dense_S50_ms"] / ms50, 3)
+    return res
+
+
 def torch_child(args, res):
     """Last GPU step of the run: torch's own ops in a child with a time limit."""
     t0 = time.time()
@@ -224,11 +328,22 @@ def main():
     ap.add_argument("--torch-only", action="store_true")
     ap.add_argument("--torch-timeout", type=int, default=150)
     ap.add_argument("--skip-head", action="store_true")
+    ap.add_argument("--skip-input", action="store_true")
+    ap.add_argument("--only-input", action="store_true",
+                    help="the input-pipeline leg alone, merged into an existing --out file")
     ap.add_argument("--skip-torch", action="store_true",
                     help="no torch-ops child (e.g. under a kernel trace)")
     args = ap.parse_args()
     if args.torch_only:
         print(json.dumps(front_end(TorchInception1D(), args.reps)), flush=True)
+        return
+    if args.only_input:
+        with open(args.out) as f:
+            res = json.load(f)
+        res["input_pipeline"] = input_pipeline(args.reps)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res["input_pipeline"]))
         return
     import hlhgat
     from hlhgat import _lib, ops
@@ -244,6 +359,8 @@ def main():
     res["kernels"] = kernels(mod, args.reps)
     if not args.skip_head:
         res["head_5x_skeleton"] = head(args.reps)
+    if not args.skip_input:
+        res["input_pipeline"] = input_pipeline(args.reps)
     ops.check_device_errors()
     torch.cuda.synchronize()
     if not args.skip_torch:
