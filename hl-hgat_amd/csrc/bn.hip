@@ -46,7 +46,6 @@
 #include "gemm_core.h"
 
 #include <atomic>
-#include <cstdlib>
 
 using namespace hlhgat;
 
@@ -88,7 +87,7 @@ bool bn_one_launch() { return bn_one_launch_flag(); }
 // 281.8k, 128 -> 287.2k, 256 -> 286.1k, 32 -> 265.8k graphs/s), one per 512
 // rows above (config 3 / 5 heads, 1.4e5-2e5 rows: 64 workgroups left most of
 // the 256 CUs idle).
-int64_t bn_parts(int64_t n, int64_t min_parts = 128) {
+int64_t bn_parts(int64_t n, int64_t min_parts) {
   int64_t p = std::max<int64_t>(min_parts, ceil_div(n, (int64_t)512));
   // small batches (the readout MLP: one row per graph): >= 64 rows per
   // partition, so the finaliser's partial loads stay one batch deep
@@ -96,33 +95,20 @@ int64_t bn_parts(int64_t n, int64_t min_parts = 128) {
   return p < 1 ? 1 : (p > kMaxParts ? kMaxParts : p);
 }
 
-// HLHGAT_BN_BWD_PARTS: minimum row partitions of the backward reduction
-// (default 128, the forward's; A/B)
-int64_t bn_bwd_min_parts() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("HLHGAT_BN_BWD_PARTS");
-    const int64_t p = e ? (int64_t)std::atoll(e) : 128;
-    return p < 1 ? (int64_t)1 : (p > kMaxParts ? (int64_t)kMaxParts : p);
-  }();
-  return v;
-}
+// Minimum row partitions of the backward reduction: the forward's 128 (A/B in
+// the config-2 step, DESIGN.md §23: 256 partitions 3.68-3.76 % against 3.93 %
+// gained, 64 partitions slower on both arms).
+constexpr int64_t kBwdMinParts = 128;
 
 // The backward reduction's partials go through the two-level tree (groups of
 // kGroup) from 16 partitions up: same-box A/B at config 2 (128 partitions,
 // profiles/r05/ab_cfg2_bn_bwd_tree.txt) 2.695 vs 2.710-2.718 ms with the flat
 // pass.  (The backward has one path, so no other launch's summation order has
 // to match it; the forward keeps the flat order its one- and two-launch paths
-// share.)  HLHGAT_BN_BWD_FLAT_MAX overrides (A/B).
-int bn_bwd_flat_max() {
-  static const int v = [] {
-    const char* e = std::getenv("HLHGAT_BN_BWD_FLAT_MAX");
-    const int f = e ? std::atoi(e) : kGroup;
-    return f < 1 ? 1 : (f > kFlatMax ? kFlatMax : f);
-  }();
-  return v;
-}
+// share.)
+constexpr int kBwdFlatMax = kGroup;
 
-BnLayout bn_layout(int64_t n, int64_t C, bool vec, int64_t min_parts = 128) {
+BnLayout bn_layout(int64_t n, int64_t C, bool vec, int64_t min_parts) {
   BnLayout L;
   L.v = vec ? 4 : 1;
   int lanes = (int)ceil_div(C, L.v);
@@ -151,29 +137,28 @@ struct BnWs {
 
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
-// Counters live at a FIXED offset so a launch with a different (n, C) never
-// reads another launch's partials as a counter.
-size_t bn_ws_bytes(int64_t n, int64_t C) {
-  (void)n;
-  return align_up(sizeof(unsigned) * kCounters) + align_up(sizeof(unsigned long long) * kMaxSlots) +
-         align_up(sizeof(double) * 2 * kMaxParts * C) +
-         align_up(sizeof(double) * 2 * kMaxGroups * C) + align_up(sizeof(float) * 3 * C);
+// The workspace layout, stated once: carves `ws` (NULL: sizes only) into `w`
+// and returns the bytes a C-column call needs.  Counters live at a FIXED
+// offset so a launch with a different (n, C) never reads another launch's
+// partials as a counter.
+size_t carve(void* ws, int64_t C, BnWs& w) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = ws ? (char*)ws + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  };
+  w.count = (unsigned*)take(sizeof(unsigned) * kCounters);
+  w.slots = (unsigned long long*)take(sizeof(unsigned long long) * kMaxSlots);
+  w.part = (double*)take(sizeof(double) * 2 * kMaxParts * C);
+  w.gpart = (double*)take(sizeof(double) * 2 * kMaxGroups * C);
+  w.coef = (float*)take(sizeof(float) * 3 * C);
+  return off;
 }
 
-BnWs carve(void* ws, int64_t n, int64_t C) {
-  (void)n;
-  char* p = (char*)ws;
+size_t bn_ws_bytes(int64_t C) {
   BnWs w;
-  w.count = (unsigned*)p;
-  p += align_up(sizeof(unsigned) * kCounters);
-  w.slots = (unsigned long long*)p;
-  p += align_up(sizeof(unsigned long long) * kMaxSlots);
-  w.part = (double*)p;
-  p += align_up(sizeof(double) * 2 * kMaxParts * C);
-  w.gpart = (double*)p;
-  p += align_up(sizeof(double) * 2 * kMaxGroups * C);
-  w.coef = (float*)p;
-  return w;
+  return carve(nullptr, C, w);
 }
 
 // n_valid (optional, device int32): only rows [0, min(n, *n_valid)) are
@@ -460,15 +445,15 @@ __device__ __forceinline__ unsigned bar_wait(unsigned long long* word, unsigned 
 }
 
 // the barrier word of this launch's column tile (8-byte aligned: kGridBase is even)
-__device__ __forceinline__ unsigned long long* barrier_word(const StatsArgs& a, const Blk& blk) {
-  return reinterpret_cast<unsigned long long*>(a.count + kGridBase) + blk.y;
+__device__ __forceinline__ unsigned long long* barrier_word(const StatsArgs& a) {
+  return reinterpret_cast<unsigned long long*>(a.count + kGridBase) + blockIdx.y;
 }
 
 // Block-level column partials: threads (row group rg, column lane cl) hold V
 // columns each; reduce over the rp row groups through LDS in fixed order.
 template <int V, int NT>
 __device__ __forceinline__ void write_partials(double (&s0)[V], double (&s1)[V],
-                                               const StatsArgs& a, int c0, const Blk& blk) {
+                                               const StatsArgs& a, int c0) {
   __shared__ double red[2][NT * 4];
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
@@ -486,7 +471,7 @@ __device__ __forceinline__ void write_partials(double (&s0)[V], double (&s1)[V],
     }
     const int c = c0 + t;
     if (c < a.C) {
-      double* dst = a.part + ((int64_t)blk.x * a.C + c) * 2;
+      double* dst = a.part + ((int64_t)blockIdx.x * a.C + c) * 2;
       st_wt(dst, u0);
       st_wt(dst + 1, u1);
     }
@@ -593,14 +578,14 @@ __device__ __forceinline__ void reduce_range(const double* src, int first, int c
 // (one arrival counter), else a two-level last-arriver tree.
 template <int NT>
 __device__ __forceinline__ bool last_reduce(const StatsArgs& a, int c0, int tile_c,
-                                            double* out0, double* out1, const Blk& blk) {
-  const int tile = blk.y;
+                                            double* out0, double* out1) {
+  const int tile = blockIdx.y;
   if (a.parts <= a.flat_max) {
     if (!arrive_last(a.count + tile, (unsigned)a.parts, a.err)) return false;
     flat_reduce<NT>(a.part, a.parts, a, c0, tile_c, out0, out1);
     return true;
   }
-  const int g = blk.x / kGroup;
+  const int g = blockIdx.x / kGroup;
   const int ng = (a.parts + kGroup - 1) / kGroup;
   const int first = g * kGroup;
   const int cnt = a.parts - first < kGroup ? a.parts - first : kGroup;
@@ -662,27 +647,32 @@ __device__ __forceinline__ void bwd_coefs(float is_f, float w_f, double sg, doub
 // (layout [S0[C], S1[C], n_eff], fp64: hlhgat_bn_sums_fwd / _bwd).
 __device__ __forceinline__ void write_sums(const StatsArgs& a, int c0, int tile_c,
                                            const double* sum0, const double* sum1,
-                                           int64_t n_eff, const Blk& blk) {
+                                           int64_t n_eff) {
   for (int t = threadIdx.x; t < tile_c; t += kThreads) {
     const int cc = c0 + t;
     if (cc >= a.C) continue;
     a.sums_out[cc] = sum0[t];
     a.sums_out[a.C + cc] = sum1[t];
   }
-  if (blk.y == 0 && threadIdx.x == 0) a.sums_out[2 * a.C] = (double)n_eff;
+  if (blockIdx.y == 0 && threadIdx.x == 0) a.sums_out[2 * a.C] = (double)n_eff;
 }
 
 // ---------------------------------------------------------------------------
 // two-launch path
+//
+// k_bn_stats, k_bn_bwd_reduce, k_bn_fwd_grid and k_bn_bwd_grid are a body that
+// takes its arguments by reference plus a one-line kernel: written straight
+// into the kernel, the same statements compile to other (equivalent) code, and
+// these kernels' code is kept as measured.
 // ---------------------------------------------------------------------------
 template <int V>
-__device__ __forceinline__ void k_bn_stats_body(const StatsArgs& a, Blk blk) {
+__device__ __forceinline__ void k_bn_stats_body(const StatsArgs& a) {
   using vt = typename VecT<V>::type;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c0 = blk.y * a.tpr * V;
+  const int c0 = blockIdx.y * a.tpr * V;
   const int c = c0 + cl * V;
-  const int64_t r_lo = (int64_t)blk.x * a.rows_per_part;
+  const int64_t r_lo = (int64_t)blockIdx.x * a.rows_per_part;
   int64_t r_hi = r_lo + a.rows_per_part;
   const int64_t n_eff = eff_rows(a.n, a.nvalid);
   if (r_hi > n_eff) r_hi = n_eff;
@@ -714,12 +704,12 @@ __device__ __forceinline__ void k_bn_stats_body(const StatsArgs& a, Blk blk) {
       }
     }
   }
-  write_partials<V, kThreads>(s0, s1, a, c0, blk);
+  write_partials<V, kThreads>(s0, s1, a, c0);
   __shared__ double sum0[kThreads], sum1[kThreads];
   const int tile_c = a.tpr * V;
-  if (!last_reduce<kThreads>(a, c0, tile_c, sum0, sum1, blk)) return;
+  if (!last_reduce<kThreads>(a, c0, tile_c, sum0, sum1)) return;
   if (a.sums_out) {  // SyncBatchNorm: this rank's sums, finalised after the all-gather
-    write_sums(a, c0, tile_c, sum0, sum1, n_eff, blk);
+    write_sums(a, c0, tile_c, sum0, sum1, n_eff);
     return;
   }
   for (int t = threadIdx.x; t < tile_c; t += kThreads) {
@@ -730,12 +720,12 @@ __device__ __forceinline__ void k_bn_stats_body(const StatsArgs& a, Blk blk) {
     a.save_mean[cc] = m;
     a.save_invstd[cc] = is;
   }
-  if (a.nbt && blk.y == 0 && threadIdx.x == 0) a.nbt[0] += 1;
+  if (a.nbt && blockIdx.y == 0 && threadIdx.x == 0) a.nbt[0] += 1;
 }
 
 template <int V>
 __global__ __launch_bounds__(kThreads) void k_bn_stats(StatsArgs a) {
-  k_bn_stats_body<V>(a, blk_hw());
+  k_bn_stats_body<V>(a);
 }
 
 struct ApplyArgs {
@@ -758,12 +748,42 @@ struct ApplyArgs {
   float eps;
 };
 
+// The row loop of k_bn_apply and k_bn_sync_apply: thread (rg, column c) writes
+// APPLY_RPT rows of y from its columns' (mean, scale, shift); all loads are
+// issued before any store; rows from n_eff up are written as 0.
 template <int V>
-__device__ __forceinline__ void k_bn_apply_body(const ApplyArgs& a, Blk blk) {
+__device__ __forceinline__ void bn_apply_rows(const float* x, int64_t ldx, float* y, int64_t ldy,
+                                              int64_t n, const int32_t* nvalid, int rp, int rg,
+                                              int c, const float (&m)[V], const float (&s)[V],
+                                              const float (&t)[V], int relu) {
   using vt = typename VecT<V>::type;
+  const int64_t n_eff = eff_rows(n, nvalid);
+  const int64_t r0 = (int64_t)blockIdx.x * rp * APPLY_RPT + rg;
+  vt xv[APPLY_RPT];
+#pragma unroll
+  for (int u = 0; u < APPLY_RPT; ++u) {
+    const int64_t r = r0 + u * rp;
+    if (r < n_eff) xv[u] = vload<V>(x + r * ldx + c);
+  }
+#pragma unroll
+  for (int u = 0; u < APPLY_RPT; ++u) {
+    const int64_t r = r0 + u * rp;
+    if (r >= n) break;
+    vt o;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float z = (vget(xv[u], v) - m[v]) * s[v] + t[v];
+      vget(o, v) = r >= n_eff ? 0.f : ((relu && z < 0.f) ? 0.f : z);
+    }
+    vstore<V>(y + r * ldy + c, o);
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void k_bn_apply(ApplyArgs a) {
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c = blk.y * a.tpr * V + cl * V;
+  const int c = blockIdx.y * a.tpr * V + cl * V;
   if (c >= a.C) return;
   float s[V], m[V], t[V];
 #pragma unroll
@@ -774,32 +794,7 @@ __device__ __forceinline__ void k_bn_apply_body(const ApplyArgs& a, Blk blk) {
     m[v] = a.mean[c + v];
     t[v] = a.bias ? a.bias[c + v] : 0.f;
   }
-  // APPLY_RPT rows per thread, all loads issued before any store
-  const int64_t n_eff = eff_rows(a.n, a.nvalid);
-  const int64_t r0 = (int64_t)blk.x * a.rp * APPLY_RPT + rg;
-  vt xv[APPLY_RPT];
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r < n_eff) xv[u] = vload<V>(a.x + r * a.ldx + c);
-  }
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r >= a.n) break;
-    vt o;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      float z = (vget(xv[u], v) - m[v]) * s[v] + t[v];
-      vget(o, v) = r >= n_eff ? 0.f : ((a.relu && z < 0.f) ? 0.f : z);
-    }
-    vstore<V>(a.y + r * a.ldy + c, o);
-  }
-}
-
-template <int V>
-__global__ __launch_bounds__(kThreads) void k_bn_apply(ApplyArgs a) {
-  k_bn_apply_body<V>(a, blk_hw());
+  bn_apply_rows<V>(a.x, a.ldx, a.y, a.ldy, a.n, a.nvalid, a.rp, rg, c, m, s, t, a.relu);
 }
 
 struct BwdApplyArgs {
@@ -823,13 +818,13 @@ struct BwdApplyArgs {
 // the finalising workgroup of a column tile forms dweight, dbias and dx's
 // coefficients.
 template <int V>
-__device__ __forceinline__ void k_bn_bwd_reduce_body(const StatsArgs& a, Blk blk) {
+__device__ __forceinline__ void k_bn_bwd_reduce_body(const StatsArgs& a) {
   using vt = typename VecT<V>::type;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c0 = blk.y * a.tpr * V;
+  const int c0 = blockIdx.y * a.tpr * V;
   const int c = c0 + cl * V;
-  const int64_t r_lo = (int64_t)blk.x * a.rows_per_part;
+  const int64_t r_lo = (int64_t)blockIdx.x * a.rows_per_part;
   int64_t r_hi = r_lo + a.rows_per_part;
   const int64_t n_eff = eff_rows(a.n, a.nvalid);
   if (r_hi > n_eff) r_hi = n_eff;
@@ -871,12 +866,12 @@ __device__ __forceinline__ void k_bn_bwd_reduce_body(const StatsArgs& a, Blk blk
       acc(xv, gv, yv);
     }
   }
-  write_partials<V, kThreads>(s0, s1, a, c0, blk);
+  write_partials<V, kThreads>(s0, s1, a, c0);
   __shared__ double sum0[kThreads], sum1[kThreads];
   const int tile_c = a.tpr * V;
-  if (!last_reduce<kThreads>(a, c0, tile_c, sum0, sum1, blk)) return;
+  if (!last_reduce<kThreads>(a, c0, tile_c, sum0, sum1)) return;
   if (a.sums_out) {  // SyncBatchNorm: local dweight / dbias, global coefficients later
-    write_sums(a, c0, tile_c, sum0, sum1, n_eff, blk);
+    write_sums(a, c0, tile_c, sum0, sum1, n_eff);
     for (int t = threadIdx.x; t < tile_c; t += kThreads) {
       const int cc = c0 + t;
       if (cc >= a.C) continue;
@@ -901,29 +896,59 @@ __device__ __forceinline__ void k_bn_bwd_reduce_body(const StatsArgs& a, Blk blk
 
 template <int V>
 __global__ __launch_bounds__(kThreads) void k_bn_bwd_reduce(StatsArgs a) {
-  k_bn_bwd_reduce_body<V>(a, blk_hw());
-}
-
-void launch_bwd_reduce(bool vec, dim3 grid, hipStream_t st, ProfScope* prof, const StatsArgs& s) {
-  if (vec)
-    launch(k_bn_bwd_reduce<4>, grid, dim3(kThreads), 0, st, prof, s);
-  else
-    launch(k_bn_bwd_reduce<1>, grid, dim3(kThreads), 0, st, prof, s);
+  k_bn_bwd_reduce_body<V>(a);
 }
 
 // dx of one element from the masked gradient g and xc = x - mean: the ONE
-// expression of k_bn_bwd_apply and k_bn_bwd_grid (the same operations, so the
-// same bits whichever kernel writes a row).
+// expression of every backward kernel (the same operations, so the same bits
+// whichever kernel writes a row).
 __device__ __forceinline__ float bn_dx(float A, float g, float B, float xc, float Cc) {
   return A * g + (B * xc + Cc);
 }
 
+// The row loop of k_bn_bwd_apply and k_bn_sync_bwd_apply: thread (rg, column
+// c) writes APPLY_RPT rows of dx from its columns' (A, B, C, mean); y (or
+// NULL) masks dy; rows from n_eff up are written as 0.
 template <int V>
-__device__ __forceinline__ void k_bn_bwd_apply_body(const BwdApplyArgs& a, Blk blk) {
+__device__ __forceinline__ void bn_bwd_apply_rows(const float* x, int64_t ldx, const float* y,
+                                                  int64_t ldy, const float* dy, int64_t lddy,
+                                                  float* dx, int64_t lddx, int64_t n,
+                                                  const int32_t* nvalid, int rp, int rg, int c,
+                                                  const float (&A)[V], const float (&B)[V],
+                                                  const float (&Cc)[V], const float (&mu)[V]) {
   using vt = typename VecT<V>::type;
+  const int64_t n_eff = eff_rows(n, nvalid);
+  const int64_t r0 = (int64_t)blockIdx.x * rp * APPLY_RPT + rg;
+  vt xv[APPLY_RPT], gv[APPLY_RPT], yv[APPLY_RPT];
+#pragma unroll
+  for (int u = 0; u < APPLY_RPT; ++u) {
+    const int64_t r = r0 + u * rp;
+    if (r < n_eff) {
+      xv[u] = vload<V>(x + r * ldx + c);
+      gv[u] = vload<V>(dy + r * lddy + c);
+      if (y) yv[u] = vload<V>(y + r * ldy + c);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < APPLY_RPT; ++u) {
+    const int64_t r = r0 + u * rp;
+    if (r >= n) break;
+    vt o;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float g = vget(gv[u], v);
+      if (y && !(vget(yv[u], v) > 0.f)) g = 0.f;
+      vget(o, v) = r >= n_eff ? 0.f : bn_dx(A[v], g, B[v], vget(xv[u], v) - mu[v], Cc[v]);
+    }
+    vstore<V>(dx + r * lddx + c, o);
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(BwdApplyArgs a) {
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c = blk.y * a.tpr * V + cl * V;
+  const int c = blockIdx.y * a.tpr * V + cl * V;
   if (c >= a.C) return;
   float A[V], B[V], Cc[V], mu[V];
 #pragma unroll
@@ -933,36 +958,8 @@ __device__ __forceinline__ void k_bn_bwd_apply_body(const BwdApplyArgs& a, Blk b
     Cc[v] = a.coef[2 * a.C + c + v];
     mu[v] = a.mean[c + v];
   }
-  const int64_t n_eff = eff_rows(a.n, a.nvalid);
-  const int64_t r0 = (int64_t)blk.x * a.rp * APPLY_RPT + rg;
-  vt xv[APPLY_RPT], gv[APPLY_RPT], yv[APPLY_RPT];
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r < n_eff) {
-      xv[u] = vload<V>(a.x + r * a.ldx + c);
-      gv[u] = vload<V>(a.dy + r * a.lddy + c);
-      if (a.y) yv[u] = vload<V>(a.y + r * a.ldy + c);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r >= a.n) break;
-    vt o;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      float g = vget(gv[u], v);
-      if (a.y && !(vget(yv[u], v) > 0.f)) g = 0.f;
-      vget(o, v) = r >= n_eff ? 0.f : bn_dx(A[v], g, B[v], vget(xv[u], v) - mu[v], Cc[v]);
-    }
-    vstore<V>(a.dx + r * a.lddx + c, o);
-  }
-}
-
-template <int V>
-__global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(BwdApplyArgs a) {
-  k_bn_bwd_apply_body<V>(a, blk_hw());
+  bn_bwd_apply_rows<V>(a.x, a.ldx, a.y, a.ldy, a.dy, a.lddy, a.dx, a.lddx, a.n, a.nvalid, a.rp, rg,
+                       c, A, B, Cc, mu);
 }
 
 // ---------------------------------------------------------------------------
@@ -1013,7 +1010,6 @@ __device__ __forceinline__ void sync_totals(const SyncArgs& a, int cc, double& s
 
 template <int V>
 __global__ __launch_bounds__(kThreads) void k_bn_sync_apply(SyncArgs a) {
-  using vt = typename VecT<V>::type;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
   const int c = blockIdx.y * a.tpr * V + cl * V;
@@ -1037,31 +1033,11 @@ __global__ __launch_bounds__(kThreads) void k_bn_sync_apply(SyncArgs a) {
     t[v] = a.bias ? a.bias[c + v] : 0.f;
   }
   if (a.nbt && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.nbt[0] += 1;
-  const int64_t n_eff = eff_rows(a.n, a.nvalid);
-  const int64_t r0 = (int64_t)blockIdx.x * a.rp * APPLY_RPT + rg;
-  vt xv[APPLY_RPT];
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r < n_eff) xv[u] = vload<V>(a.x + r * a.ldx + c);
-  }
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r >= a.n) break;
-    vt o;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      float z = (vget(xv[u], v) - m[v]) * s[v] + t[v];
-      vget(o, v) = r >= n_eff ? 0.f : ((a.relu && z < 0.f) ? 0.f : z);
-    }
-    vstore<V>(a.out + r * a.ldo + c, o);
-  }
+  bn_apply_rows<V>(a.x, a.ldx, a.out, a.ldo, a.n, a.nvalid, a.rp, rg, c, m, s, t, a.relu);
 }
 
 template <int V>
 __global__ __launch_bounds__(kThreads) void k_bn_sync_bwd_apply(SyncArgs a) {
-  using vt = typename VecT<V>::type;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
   const int c = blockIdx.y * a.tpr * V + cl * V;
@@ -1075,31 +1051,8 @@ __global__ __launch_bounds__(kThreads) void k_bn_sync_bwd_apply(SyncArgs a) {
               Cc[v]);
     mu[v] = a.save_mean[c + v];
   }
-  const int64_t n_eff = eff_rows(a.n, a.nvalid);
-  const int64_t r0 = (int64_t)blockIdx.x * a.rp * APPLY_RPT + rg;
-  vt xv[APPLY_RPT], gv[APPLY_RPT], yv[APPLY_RPT];
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r < n_eff) {
-      xv[u] = vload<V>(a.x + r * a.ldx + c);
-      gv[u] = vload<V>(a.dy + r * a.lddy + c);
-      if (a.y) yv[u] = vload<V>(a.y + r * a.ldy + c);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < APPLY_RPT; ++u) {
-    const int64_t r = r0 + u * a.rp;
-    if (r >= a.n) break;
-    vt o;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      float g = vget(gv[u], v);
-      if (a.y && !(vget(yv[u], v) > 0.f)) g = 0.f;
-      vget(o, v) = r >= n_eff ? 0.f : A[v] * g + (B[v] * (vget(xv[u], v) - mu[v]) + Cc[v]);
-    }
-    vstore<V>(a.out + r * a.ldo + c, o);
-  }
+  bn_bwd_apply_rows<V>(a.x, a.ldx, a.y, a.ldy, a.dy, a.lddy, a.out, a.ldo, a.n, a.nvalid, a.rp, rg,
+                       c, A, B, Cc, mu);
 }
 
 // ---------------------------------------------------------------------------
@@ -1122,14 +1075,16 @@ __device__ __forceinline__ typename VecT<V>::type bn_row_out(typename VecT<V>::t
   return o;
 }
 
+
 template <int V, int RPT>
-__device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a, Blk blk) {
+__device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a) {
+  const unsigned gx = gridDim.x;  // the partitions of a column tile
   using vt = typename VecT<V>::type;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c0 = blk.y * a.tpr * V;
+  const int c0 = blockIdx.y * a.tpr * V;
   const int c = c0 + cl * V;
-  const int64_t r_lo = (int64_t)blk.x * a.rows_per_part;
+  const int64_t r_lo = (int64_t)blockIdx.x * a.rows_per_part;
   const int64_t n_eff = eff_rows(a.n, a.nvalid);
   int64_t r_hi = r_lo + a.rows_per_part;
   if (r_hi > n_eff) r_hi = n_eff;
@@ -1164,16 +1119,16 @@ __device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a, Blk blk) 
     wv[v] = (a.weight && in) ? a.weight[c + v] : 1.f;
     bv[v] = (a.bias && in) ? a.bias[c + v] : 0.f;
   }
-  write_partials<V, kThreads>(s0, s1, a, c0, blk);
-  unsigned long long* tile_slots = a.slots + (int64_t)blk.y * blk.gx;
+  write_partials<V, kThreads>(s0, s1, a, c0);
+  unsigned long long* tile_slots = a.slots + (int64_t)blockIdx.y * gx;
   unsigned gen0 = 0;
   const unsigned role =
-      bar_wait(barrier_word(a, blk), tile_slots + blk.x, blk.gx, a.wait_us, a.err, &gen0);
+      bar_wait(barrier_word(a), tile_slots + blockIdx.x, gx, a.wait_us, a.err, &gen0);
   if (role == kLeft) return;  // the finaliser normalises these rows
   __shared__ double sum0[kThreads], sum1[kThreads];
   __shared__ float sm[kThreads], ss[kThreads];
   const int tile_c = a.tpr * V;
-  flat_reduce<kThreads>(a.part, blk.gx, a, c0, tile_c, sum0, sum1);
+  flat_reduce<kThreads>(a.part, gx, a, c0, tile_c, sum0, sum1);
   // the finaliser writes the saved and running statistics (exactly once)
   const bool fin = role == kFinal;
   for (int t = threadIdx.x; t < tile_c; t += kThreads) {
@@ -1189,7 +1144,7 @@ __device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a, Blk blk) 
     sm[t] = m;
     ss[t] = is;
   }
-  if (fin && a.nbt && blk.y == 0 && threadIdx.x == 0) a.nbt[0] += 1;
+  if (fin && a.nbt && blockIdx.y == 0 && threadIdx.x == 0) a.nbt[0] += 1;
   __syncthreads();
   float sc[V], mu[V], sh[V];
 #pragma unroll
@@ -1210,9 +1165,9 @@ __device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a, Blk blk) 
   if (!fin) return;
   // rows of partitions whose owners gave up: from x in memory, same operations
   __shared__ unsigned char taken[kMaxParts];
-  if (!take_left<kThreads>(tile_slots, (int)blk.gx, gen0, taken)) return;
+  if (!take_left<kThreads>(tile_slots, (int)gx, gen0, taken)) return;
   if (c >= a.C) return;
-  for (unsigned p = 0; p < blk.gx; ++p) {
+  for (unsigned p = 0; p < gx; ++p) {
     if (!taken[p]) continue;
     const int64_t p_lo = (int64_t)p * a.rows_per_part;
     int64_t p_end = p_lo + a.rows_per_part;
@@ -1226,7 +1181,7 @@ __device__ __forceinline__ void k_bn_fwd_grid_body(const StatsArgs& a, Blk blk) 
 
 template <int V, int RPT>
 __global__ __launch_bounds__(kThreads) void k_bn_fwd_grid(StatsArgs a) {
-  k_bn_fwd_grid_body<V, RPT>(a, blk_hw());
+  k_bn_fwd_grid_body<V, RPT>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -1491,7 +1446,7 @@ __global__ __launch_bounds__(kThreads) void k_proj_bn_fwd(ProjBnArgs a) {
 // (rg, cl) owns rows r_lo + rg + j * rp (j < RPT) of its partition:
 //   1. each owned row's x, dy (and y) is loaded once; the masked gradient g
 //      and xc = x - mean stay in registers, the fp64 partials are summed in
-//      ascending row order (k_bn_bwd_reduce_body's operations) and written
+//      ascending row order (k_bn_bwd_reduce's operations) and written
 //      through;
 //   2. last_reduce's tree, unchanged; its last arriver forms dweight, dbias
 //      and dx's coefficients, writes the coefficients through, drains the
@@ -1506,15 +1461,16 @@ __global__ __launch_bounds__(kThreads) void k_proj_bn_fwd(ProjBnArgs a) {
 // wait is bounded and ends in a hand-over; nothing depends on co-residency.
 // ---------------------------------------------------------------------------
 template <int V, int RPT>
-__device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) {
+__device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a) {
+  const unsigned gx = gridDim.x;  // the partitions of a column tile
   using vt = typename VecT<V>::type;
   constexpr int CH = RPT < 4 ? RPT : 4;  // rows (3 loads each) in flight, as k_bn_bwd_reduce
   __shared__ unsigned s_gen0, s_ok;
   const int cl = threadIdx.x % a.tpr;
   const int rg = threadIdx.x / a.tpr;
-  const int c0 = blk.y * a.tpr * V;
+  const int c0 = blockIdx.y * a.tpr * V;
   const int c = c0 + cl * V;
-  const int64_t r_lo = (int64_t)blk.x * a.rows_per_part;
+  const int64_t r_lo = (int64_t)blockIdx.x * a.rows_per_part;
   const int64_t n_eff = eff_rows(a.n, a.nvalid);
   int64_t r_hi = r_lo + a.rows_per_part;
   if (r_hi > n_eff) r_hi = n_eff;
@@ -1572,15 +1528,15 @@ __device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) 
   const bool fcol = (int)threadIdx.x < tile_c && fc < a.C;
   const float f_is = fcol ? a.save_invstd[fc] : 0.f;
   const float f_w = (fcol && a.weight) ? a.weight[fc] : 1.f;
-  write_partials<V, kThreads>(s0, s1, a, c0, blk);
-  unsigned long long* word = gen_word(a, blk.y);
+  write_partials<V, kThreads>(s0, s1, a, c0);
+  unsigned long long* word = gen_word(a, blockIdx.y);
   if (threadIdx.x == 0)  // the generation before this workgroup's arrival
     s_gen0 = (unsigned)(__hip_atomic_load((gu64c_t*)word, __ATOMIC_RELAXED,
                                           __HIP_MEMORY_SCOPE_AGENT) >> 32);
   __shared__ double sum0[kThreads], sum1[kThreads];
   __shared__ float sA[kThreads], sB[kThreads], sC[kThreads];
-  unsigned long long* tile_slots = a.slots + (int64_t)blk.y * blk.gx;
-  const bool fin = last_reduce<kThreads>(a, c0, tile_c, sum0, sum1, blk);
+  unsigned long long* tile_slots = a.slots + (int64_t)blockIdx.y * gx;
+  const bool fin = last_reduce<kThreads>(a, c0, tile_c, sum0, sum1);
   if (fin) {
     if ((int)threadIdx.x < tile_c) {  // tile_c <= kThreads: one column per thread
       const int t = threadIdx.x, cc = fc;
@@ -1610,7 +1566,7 @@ __device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) 
         const unsigned total = a.parts <= a.flat_max
                                    ? (unsigned)a.parts
                                    : (unsigned)((a.parts + kGroup - 1) / kGroup);
-        ok = give_up(word, tile_slots + blk.x, s_gen0, kKidBnBwd, a.count + blk.y, false, total,
+        ok = give_up(word, tile_slots + blockIdx.x, s_gen0, kKidBnBwd, a.count + blockIdx.y, false, total,
                      a.wait_us)
                  ? 1u
                  : 0u;
@@ -1662,9 +1618,9 @@ __device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) 
   if (!fin) return;
   // rows of partitions whose owners gave up: from x, dy, y in memory, same operations
   __shared__ unsigned char taken[kMaxParts];
-  if (!take_left<kThreads>(tile_slots, (int)blk.gx, s_gen0, taken)) return;
+  if (!take_left<kThreads>(tile_slots, (int)gx, s_gen0, taken)) return;
   if (c >= a.C) return;
-  for (unsigned p = 0; p < blk.gx; ++p) {
+  for (unsigned p = 0; p < gx; ++p) {
     if (!taken[p]) continue;
     const int64_t p_lo = (int64_t)p * a.rows_per_part;
     int64_t p_end = p_lo + a.rows_per_part;
@@ -1693,7 +1649,7 @@ __device__ __forceinline__ void k_bn_bwd_grid_body(const StatsArgs& a, Blk blk) 
 
 template <int V, int RPT>
 __global__ __launch_bounds__(kThreads) void k_bn_bwd_grid(StatsArgs a) {
-  k_bn_bwd_grid_body<V, RPT>(a, blk_hw());
+  k_bn_bwd_grid_body<V, RPT>(a);
 }
 
 bool& proj_bn_fused_flag() {
@@ -1716,55 +1672,190 @@ bool& proj_bn_split_flag() {
   return v;
 }
 
-bool bn_vec_ok(int64_t C, std::initializer_list<int64_t> lds,
-               std::initializer_list<const void*> ptrs) {
-  if (C % 4) return false;
-  for (int64_t ld : lds)
-    if (ld % 4) return false;
-  for (const void* p : ptrs)
-    if (p && !aligned16(p)) return false;
-  return true;
-}
+// --- one description of a call ---------------------------------------------
+// A row buffer of a call and its leading dimension.  p == NULL: not given (an
+// optional y; a dx named only for its layout) -- not checked, and no obstacle
+// to the vector path.
+struct BnBuf {
+  const void* p;
+  int64_t ld;
+};
 
-unsigned apply_grid_x(int64_t n, int rp) {
-  int64_t g = ceil_div(n, (int64_t)rp * APPLY_RPT);  // every row owned by one thread
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
+struct BnWsArg {  // {} for an entry point that takes no workspace
+  void* p = nullptr;
+  int64_t bytes = 0;
+  bool taken = false;
+};
 
-StatsArgs stats_args(const BnLayout& L, const BnWs& w, const float* x, int64_t ldx, int64_t n,
-                     const int32_t* n_valid, int64_t C) {
+// What an entry point derives from its arguments: the vector width, the
+// layout, the summation order of the partials and the carved workspace.
+// Launches whose results must agree bit for bit (one launch / two launches /
+// SyncBatchNorm) agree because they are built by the same constructor over
+// the same buffers.
+struct BnCall {
+  int64_t n, C;
+  bool vec;       // float4 rows: C, every ld and every pointer allow it
+  BnLayout L;
+  int flat_max;   // last_reduce: one flat pass up to this many partitions
+  BnWs w;         // NULL pointers where no workspace is taken
+
+  dim3 stats_grid() const { return dim3(L.parts, L.tiles); }
+  dim3 apply_grid() const {  // every row owned by one thread
+    int64_t g = ceil_div(n, (int64_t)L.rp * APPLY_RPT);
+    return dim3((unsigned)(g < 1 ? 1 : g), L.tiles);
+  }
+
+  // The forward layout over (x, y): 128 partitions at least, the flat order.
+  static int forward(BnCall& c, const char* who, int64_t n, int64_t C,
+                     std::initializer_list<BnBuf> bufs, BnWsArg ws = {}) {
+    return c.init(who, n, C, 128, kFlatMax, bufs, ws);
+  }
+  // The backward layout over (x, y, dy, dx): kBwdMinParts, the tree from
+  // kBwdFlatMax partitions up.
+  static int backward(BnCall& c, const char* who, int64_t n, int64_t C,
+                      std::initializer_list<BnBuf> bufs, BnWsArg ws = {}) {
+    return c.init(who, n, C, kBwdMinParts, kBwdFlatMax, bufs, ws);
+  }
+
+ private:
+  // The checks every entry point shares (`who` prefixes the message): sizes,
+  // workspace, column tiles.  C < 2^20 also keeps bn_layout's ints in range.
+  int init(const char* who, int64_t n_, int64_t C_, int64_t min_parts, int flat_max_,
+           std::initializer_list<BnBuf> bufs, BnWsArg ws) {
+    bool sizes = n_ >= 1 && C_ >= 1 && C_ < (1 << 20);
+    vec = C_ % 4 == 0;
+    for (const BnBuf& b : bufs) {
+      if (!b.p) continue;
+      sizes = sizes && b.ld >= C_;
+      vec = vec && b.ld % 4 == 0 && aligned16(b.p);
+    }
+    HLH_CHECK_ARG(sizes, "%s: bad sizes n=%lld C=%lld", who, (long long)n_, (long long)C_);
+    w = BnWs{};
+    if (ws.taken)
+      HLH_CHECK_ARG(ws.p && ws.bytes >= (int64_t)carve(ws.p, C_, w), "%s: workspace too small",
+                    who);
+    n = n_;
+    C = C_;
+    flat_max = flat_max_;
+    L = bn_layout(n, C, vec, min_parts);
+    HLH_CHECK_ARG(L.tiles <= kMaxTiles, "%s: C too large", who);
+    return HLHGAT_OK;
+  }
+};
+
+// --- StatsArgs, filled in one place per direction ---------------------------
+StatsArgs stats_args(const BnCall& c, const float* x, int64_t ldx, const int32_t* n_valid) {
   StatsArgs s{};
   s.nvalid = n_valid;
   s.x = x;
   s.ldx = ldx;
-  s.n = n;
-  s.C = (int)C;
-  s.tpr = L.tpr;
-  s.rp = L.rp;
-  s.tiles = L.tiles;
-  s.parts = L.parts;
-  s.rows_per_part = L.rows_per_part;
-  s.part = w.part;
-  s.gpart = w.gpart;
-  s.count = w.count;
-  s.slots = w.slots;
+  s.n = c.n;
+  s.C = (int)c.C;
+  s.tpr = c.L.tpr;
+  s.rp = c.L.rp;
+  s.tiles = c.L.tiles;
+  s.parts = c.L.parts;
+  s.rows_per_part = c.L.rows_per_part;
+  s.part = c.w.part;
+  s.gpart = c.w.gpart;
+  s.count = c.w.count;
+  s.slots = c.w.slots;
   s.err = hlhgat::device_error_word();
-  s.flat_max = kFlatMax;
+  s.flat_max = c.flat_max;
   return s;
+}
+
+void set_fwd_final(StatsArgs& s, const float* weight, const float* bias, float* running_mean,
+                   float* running_var, int64_t* nbt, float momentum, float eps, float* save_mean,
+                   float* save_invstd) {
+  s.weight = weight;
+  s.bias = bias;
+  s.running_mean = running_mean;
+  s.running_var = running_var;
+  s.nbt = nbt;
+  s.momentum = momentum;
+  s.eps = eps;
+  s.save_mean = save_mean;
+  s.save_invstd = save_invstd;
+}
+
+void set_bwd(StatsArgs& s, const float* y, int64_t ldy, const float* dy, int64_t lddy,
+             const float* weight, const float* save_mean, const float* save_invstd, float* coef,
+             float* dweight, float* dbias) {
+  s.y = y;
+  s.ldy = ldy;
+  s.dy = dy;
+  s.lddy = lddy;
+  s.weight = weight;
+  s.save_mean = const_cast<float*>(save_mean);
+  s.save_invstd = const_cast<float*>(save_invstd);
+  s.coef = coef;
+  s.dweight = dweight;
+  s.dbias = dbias;
+}
+
+// The one-launch kernels' output rows, wait bound and error word.
+unsigned g_wait_us = 1000;
+
+int set_one_launch_out(StatsArgs& s, const char* who, float* out, int64_t ldo, int relu) {
+  s.out = out;
+  s.ldo = ldo;
+  s.relu = relu;
+  s.wait_us = g_wait_us;
+  HLH_CHECK_ARG(s.err, "%s: no device error word (%s)", who, hlhgat_last_error());
+  return HLHGAT_OK;
+}
+
+// --- each launch once -------------------------------------------------------
+// The <4> / <1> choice of a row kernel, and the launch check.
+template <typename Args>
+int launch_v(bool vec, void (*k4)(Args), void (*k1)(Args), dim3 grid, hipStream_t st,
+             const ProfScope* prof, const Args& a) {
+  launch(vec ? k4 : k1, grid, dim3(kThreads), 0, st, prof, a);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+int launch_stats(const BnCall& c, hipStream_t st, const StatsArgs& s) {
+  return launch_v(c.vec, k_bn_stats<4>, k_bn_stats<1>, c.stats_grid(), st, nullptr, s);
+}
+
+int launch_bwd_reduce(const BnCall& c, hipStream_t st, const ProfScope* prof,
+                      const StatsArgs& s) {
+  return launch_v(c.vec, k_bn_bwd_reduce<4>, k_bn_bwd_reduce<1>, c.stats_grid(), st, prof, s);
+}
+
+int launch_apply(const BnCall& c, hipStream_t st, ApplyArgs p) {
+  p.n = c.n;
+  p.C = (int)c.C;
+  p.tpr = c.L.tpr;
+  p.rp = c.L.rp;
+  return launch_v(c.vec, k_bn_apply<4>, k_bn_apply<1>, c.apply_grid(), st, nullptr, p);
+}
+
+int launch_bwd_apply(const BnCall& c, hipStream_t st, BwdApplyArgs p) {
+  p.n = c.n;
+  p.C = (int)c.C;
+  p.tpr = c.L.tpr;
+  p.rp = c.L.rp;
+  return launch_v(c.vec, k_bn_bwd_apply<4>, k_bn_bwd_apply<1>, c.apply_grid(), st, nullptr, p);
 }
 
 // --- one-launch selection: grid size and registers -------------------------
 // The one-launch kernels are taken when the grid is at most half of the
 // chip's resident-workgroup capacity for that kernel
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs / 2), at most 256
-// workgroups (the partials use the flat order) and a thread's rows fit the
-// register budget (RPT <= kMaxRpt).  That sizing is for speed only: the
-// barrier itself assumes nothing about residency (the bounded wait and the
-// finaliser's hand-over above), so a launch beside any other kernels -- the
-// other chain's barrier grid, RCCL, a whole-CU kernel -- completes with the
-// same bits, at worst one wait bound later.
-unsigned g_wait_us = 1000;
+// workgroups and a thread's rows fit the register budget (RPT <= kMaxRpt).
+// That sizing is for speed only: the barrier itself assumes nothing about
+// residency (the bounded wait and the finaliser's hand-over above), so a
+// launch beside any other kernels -- the other chain's barrier grid, RCCL, a
+// whole-CU kernel -- completes with the same bits, at worst one wait bound
+// later.
+//
+// The share of the chip one barrier grid may take is 1 / kColocate: the two
+// chains' barrier launches usually overlap (a third of the
+// chip still timed out and only shrank the set of one-launch layouts).
+constexpr int kColocate = 2;
 
 int64_t capacity_of(const void* kernel) {
   static auto* cache = new std::vector<std::pair<const void*, int64_t>>();
@@ -1772,87 +1863,54 @@ int64_t capacity_of(const void* kernel) {
     if (kv.first == kernel) return kv.second;
   int dev = 0, cus = 0, occ = 0;
   int64_t c = 0;
-  // the share of the chip one barrier grid may take: 1 / HLHGAT_BN_COLOCATE
-  // (default 2: the two chains' barrier launches usually overlap)
-  static const int share = [] {
-    const char* e = std::getenv("HLHGAT_BN_COLOCATE");
-    const int v = e ? std::atoi(e) : 2;
-    return v >= 1 && v <= 16 ? v : 2;
-  }();
   if (hipGetDevice(&dev) == hipSuccess &&
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kThreads, 0) == hipSuccess)
-    c = (int64_t)occ * cus / share;
+    c = (int64_t)occ * cus / kColocate;
   cache->push_back({kernel, c});
   return c;
 }
 
-int rpt_bucket(const BnLayout& L) {
-  const int64_t need = ceil_div(L.rows_per_part, (int64_t)L.rp);
-  if (need > kMaxRpt) return 0;
-  for (int r : {2, 4, 8, 16, 32})
-    if (need <= r) return r;
-  return 0;
-}
-
-
+// The one-launch instantiations of a direction: [vec][b], RPT = 2 << b.
 using GridFn = void (*)(StatsArgs);
-
-GridFn fwd_grid_fn(bool vec, int rpt) {
-  switch (rpt * 2 + (vec ? 1 : 0)) {
-    case 4: return k_bn_fwd_grid<1, 2>;
-    case 5: return k_bn_fwd_grid<4, 2>;
-    case 8: return k_bn_fwd_grid<1, 4>;
-    case 9: return k_bn_fwd_grid<4, 4>;
-    case 16: return k_bn_fwd_grid<1, 8>;
-    case 17: return k_bn_fwd_grid<4, 8>;
-    case 32: return k_bn_fwd_grid<1, 16>;
-    case 33: return k_bn_fwd_grid<4, 16>;
-    case 64: return k_bn_fwd_grid<1, 32>;
-    case 65: return k_bn_fwd_grid<4, 32>;
-    default: return nullptr;
-  }
+constexpr int kRptBuckets = 5;
+struct GridTable {
+  GridFn fn[2][kRptBuckets];
+};
+struct FwdGrid {
+  template <int V, int RPT>
+  static GridFn fn() { return k_bn_fwd_grid<V, RPT>; }
+};
+struct BwdGrid {
+  template <int V, int RPT>
+  static GridFn fn() { return k_bn_bwd_grid<V, RPT>; }
+};
+template <class K>
+const GridTable& grid_table() {
+  static const GridTable t = {
+      {{K::template fn<1, 2>(), K::template fn<1, 4>(), K::template fn<1, 8>(),
+        K::template fn<1, 16>(), K::template fn<1, 32>()},
+       {K::template fn<4, 2>(), K::template fn<4, 4>(), K::template fn<4, 8>(),
+        K::template fn<4, 16>(), K::template fn<4, 32>()}}};
+  return t;
 }
 
-// The one-launch kernel for this layout, or nullptr (two launches).
-GridFn pick_grid(const BnLayout& L, bool vec) {
-  if (!bn_one_launch() || L.parts > kFlatMax) return nullptr;
-  const int64_t grid = (int64_t)L.parts * L.tiles;
-  const int rpt = rpt_bucket(L);
-  GridFn f = rpt ? fwd_grid_fn(vec, rpt) : nullptr;
-  const int64_t cap = f ? capacity_of(reinterpret_cast<const void*>(f)) : 0;
-  if (!f || grid > 256 || grid > cap) return nullptr;
-  return f;
-}
-
-GridFn bwd_grid_fn(bool vec, int rpt) {
-  switch (rpt * 2 + (vec ? 1 : 0)) {
-    case 4: return k_bn_bwd_grid<1, 2>;
-    case 5: return k_bn_bwd_grid<4, 2>;
-    case 8: return k_bn_bwd_grid<1, 4>;
-    case 9: return k_bn_bwd_grid<4, 4>;
-    case 16: return k_bn_bwd_grid<1, 8>;
-    case 17: return k_bn_bwd_grid<4, 8>;
-    case 32: return k_bn_bwd_grid<1, 16>;
-    case 33: return k_bn_bwd_grid<4, 16>;
-    case 64: return k_bn_bwd_grid<1, 32>;
-    case 65: return k_bn_bwd_grid<4, 32>;
-    default: return nullptr;
-  }
-}
-
-// The one-launch backward kernel for the backward's own layout, or nullptr
-// (k_bn_bwd_reduce + k_bn_bwd_apply): both switches on, a thread's rows fit
-// the registers, the grid at most 256 workgroups and the kernel's share of the
-// chip (capacity_of).  Its partials go through last_reduce's tree, so the
-// partition count itself is not capped at kFlatMax.
-GridFn pick_bwd_grid(const BnLayout& L, bool vec) {
-  if (!bn_one_launch() || !bn_bwd_one_launch_flag()) return nullptr;
-  const int64_t grid = (int64_t)L.parts * L.tiles;
-  const int rpt = rpt_bucket(L);
-  GridFn f = rpt ? bwd_grid_fn(vec, rpt) : nullptr;
-  const int64_t cap = f ? capacity_of(reinterpret_cast<const void*>(f)) : 0;
-  if (!f || grid > 256 || grid > cap) return nullptr;
+// The one-launch kernel for this call, or nullptr (two launches): the switches
+// on, at most parts_cap partitions, a thread's rows fit the registers, the
+// grid at most 256 workgroups and the kernel's share of the chip.  The forward
+// caps the partitions at kFlatMax (its partials use the flat order); the
+// backward's go through last_reduce's tree, so it does not.
+GridFn pick_grid(const BnCall& c, const GridTable& t, bool enabled, int parts_cap) {
+  if (!enabled || c.L.parts > parts_cap) return nullptr;
+  const int64_t need = ceil_div(c.L.rows_per_part, (int64_t)c.L.rp);
+  int b = 0;
+  while (b < kRptBuckets && need > (2 << b)) ++b;
+  static_assert((2 << (kRptBuckets - 1)) == kMaxRpt, "the last bucket is kMaxRpt rows");
+  if (b == kRptBuckets) return nullptr;
+  GridFn f = t.fn[c.vec ? 1 : 0][b];
+  const int64_t grid = (int64_t)c.L.parts * c.L.tiles;
+  const int64_t cap = capacity_of(reinterpret_cast<const void*>(f));
+  if (grid > 256 || grid > cap) return nullptr;
   return f;
 }
 
@@ -1861,7 +1919,7 @@ GridFn pick_bwd_grid(const BnLayout& L, bool vec) {
 
 extern "C" int64_t hlhgat_bn_workspace_bytes(int64_t n, int64_t C) {
   if (n < 0 || C <= 0) return 0;
-  return (int64_t)bn_ws_bytes(n, C);
+  return (int64_t)bn_ws_bytes(C);
 }
 
 extern "C" int hlhgat_bn_stats_train(const float* x, int64_t ldx, int64_t n,
@@ -1870,76 +1928,41 @@ extern "C" int hlhgat_bn_stats_train(const float* x, int64_t ldx, int64_t n,
                                      float momentum, float eps, float* save_mean,
                                      float* save_invstd, void* workspace,
                                      int64_t workspace_bytes, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C,
-                "bn_stats_train: bad sizes n=%lld C=%lld", (long long)n, (long long)C);
   HLH_CHECK_ARG(x && save_mean && save_invstd, "bn_stats_train: NULL pointer");
   HLH_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
                 "bn_stats_train: running_mean/var must both be given or both NULL");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_stats_train: workspace too small");
-  const bool vec = bn_vec_ok(C, {ldx}, {x});
-  BnLayout L = bn_layout(n, C, vec);
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_stats_train: C too large");
-  StatsArgs s = stats_args(L, carve(workspace, n, C), x, ldx, n, n_valid, C);
-  s.running_mean = running_mean;
-  s.running_var = running_var;
-  s.nbt = num_batches_tracked;
-  s.momentum = momentum;
-  s.eps = eps;
-  s.save_mean = save_mean;
-  s.save_invstd = save_invstd;
-  hipStream_t st = as_stream(stream);
-  dim3 g1(L.parts, L.tiles);
-  if (vec)
-    launch(k_bn_stats<4>, dim3(g1), dim3(kThreads), 0, st, nullptr, s);
-  else
-    launch(k_bn_stats<1>, dim3(g1), dim3(kThreads), 0, st, nullptr, s);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  BnCall c;
+  if (int rc = BnCall::forward(c, "bn_stats_train", n, C, {{x, ldx}},
+                               {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
+  set_fwd_final(s, nullptr, nullptr, running_mean, running_var, num_batches_tracked, momentum,
+                eps, save_mean, save_invstd);
+  return launch_stats(c, as_stream(stream), s);
 }
 
 extern "C" int hlhgat_bn_apply(const float* x, int64_t ldx, int64_t n, const int32_t* n_valid,
                                int64_t C, const float* weight, const float* bias,
                                const float* save_mean, const float* save_invstd, int relu,
                                float* y, int64_t ldy, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C && ldy >= C,
-                "bn_apply: bad sizes n=%lld C=%lld", (long long)n, (long long)C);
   HLH_CHECK_ARG(x && y && save_mean && save_invstd, "bn_apply: NULL pointer");
-  const bool vec = bn_vec_ok(C, {ldx, ldy}, {x, y});
-  BnLayout L = bn_layout(n, C, vec);
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_apply: C too large");
-  ApplyArgs p{n_valid, x, ldx, y, ldy, n, (int)C, save_mean, save_invstd, weight, bias, relu,
-              L.tpr, L.rp};
-  hipStream_t st = as_stream(stream);
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_apply<4>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  else
-    launch(k_bn_apply<1>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  BnCall c;
+  if (int rc = BnCall::forward(c, "bn_apply", n, C, {{x, ldx}, {y, ldy}})) return rc;
+  return launch_apply(c, as_stream(stream),
+                      ApplyArgs{n_valid, x, ldx, y, ldy, n, (int)C, save_mean, save_invstd,
+                                weight, bias, relu});
 }
 
 extern "C" int hlhgat_bn_apply_running(const float* x, int64_t ldx, int64_t n, int64_t C,
                                        const float* weight, const float* bias,
                                        const float* running_mean, const float* running_var,
                                        float eps, int relu, float* y, int64_t ldy, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C && ldy >= C,
-                "bn_apply_running: bad sizes n=%lld C=%lld", (long long)n, (long long)C);
   HLH_CHECK_ARG(x && y && running_mean && running_var, "bn_apply_running: NULL pointer");
-  const bool vec = bn_vec_ok(C, {ldx, ldy}, {x, y});
-  BnLayout L = bn_layout(n, C, vec);
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_apply_running: C too large");
-  ApplyArgs p{nullptr, x, ldx, y, ldy, n, (int)C, running_mean, nullptr, weight, bias, relu,
-              L.tpr, L.rp, running_var, eps};
-  hipStream_t st = as_stream(stream);
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_apply<4>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  else
-    launch(k_bn_apply<1>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  BnCall c;
+  if (int rc = BnCall::forward(c, "bn_apply_running", n, C, {{x, ldx}, {y, ldy}})) return rc;
+  return launch_apply(c, as_stream(stream),
+                      ApplyArgs{nullptr, x, ldx, y, ldy, n, (int)C, running_mean, nullptr, weight,
+                                bias, relu, 0, 0, running_var, eps});
 }
 
 extern "C" int hlhgat_bn_fwd_train(const float* x, int64_t ldx, int64_t n,
@@ -1951,65 +1974,30 @@ extern "C" int hlhgat_bn_fwd_train(const float* x, int64_t ldx, int64_t n,
                                    float* save_mean, float* save_invstd,
                                    void* workspace, int64_t workspace_bytes,
                                    void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C && ldy >= C,
-                "bn_fwd_train: bad sizes n=%lld C=%lld", (long long)n, (long long)C);
   HLH_CHECK_ARG(x && y && save_mean && save_invstd, "bn_fwd_train: NULL pointer");
   HLH_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
                 "bn_fwd_train: running_mean/var must both be given or both NULL");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_fwd_train: workspace too small");
-  const bool vec = bn_vec_ok(C, {ldx, ldy}, {x, y});
-  const BnLayout L = bn_layout(n, C, vec);
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_fwd_train: C too large");
-  // the two-launch path must see the same layout (vector width) to give the
-  // same bits: both use bn_vec_ok over x AND y here
-  if (GridFn f = pick_grid(L, vec)) {
-    StatsArgs s = stats_args(L, carve(workspace, n, C), x, ldx, n, n_valid, C);
-    s.weight = weight;
-    s.bias = bias;
-    s.running_mean = running_mean;
-    s.running_var = running_var;
-    s.nbt = num_batches_tracked;
-    s.momentum = momentum;
-    s.eps = eps;
-    s.save_mean = save_mean;
-    s.save_invstd = save_invstd;
-    s.out = y;
-    s.ldo = ldy;
-    s.relu = relu;
-    s.wait_us = g_wait_us;
-    HLH_CHECK_ARG(s.err, "bn_fwd_train: no device error word (%s)", hlhgat_last_error());
+  BnCall c;
+  if (int rc = BnCall::forward(c, "bn_fwd_train", n, C, {{x, ldx}, {y, ldy}},
+                               {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
+  set_fwd_final(s, weight, bias, running_mean, running_var, num_batches_tracked, momentum, eps,
+                save_mean, save_invstd);
+  hipStream_t st = as_stream(stream);
+  if (GridFn f = pick_grid(c, grid_table<FwdGrid>(), bn_one_launch(), kFlatMax)) {
+    if (int rc = set_one_launch_out(s, "bn_fwd_train", y, ldy, relu)) return rc;
     // algorithmic bytes: x read once, y written once
-    ProfScope prof(HLHGAT_PROF_BN_FWD, as_stream(stream), 8.0 * (double)n * C, 0.0);
-    launch(f, dim3(L.parts, L.tiles), dim3(kThreads), 0, as_stream(stream), &prof, s);
+    ProfScope prof(HLHGAT_PROF_BN_FWD, st, 8.0 * (double)n * C, 0.0);
+    launch(f, c.stats_grid(), dim3(kThreads), 0, st, &prof, s);
     HLH_CHECK_LAUNCH();
     return HLHGAT_OK;
   }
   // two launches on the same layout
-  StatsArgs s = stats_args(L, carve(workspace, n, C), x, ldx, n, n_valid, C);
-  s.running_mean = running_mean;
-  s.running_var = running_var;
-  s.nbt = num_batches_tracked;
-  s.momentum = momentum;
-  s.eps = eps;
-  s.save_mean = save_mean;
-  s.save_invstd = save_invstd;
-  hipStream_t st = as_stream(stream);
-  dim3 g1(L.parts, L.tiles);
-  if (vec)
-    launch(k_bn_stats<4>, dim3(g1), dim3(kThreads), 0, st, nullptr, s);
-  else
-    launch(k_bn_stats<1>, dim3(g1), dim3(kThreads), 0, st, nullptr, s);
-  HLH_CHECK_LAUNCH();
-  ApplyArgs p{n_valid, x, ldx, y, ldy, n, (int)C, save_mean, save_invstd, weight, bias, relu,
-              L.tpr, L.rp};
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_apply<4>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  else
-    launch(k_bn_apply<1>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  if (int rc = launch_stats(c, st, s)) return rc;
+  return launch_apply(c, st,
+                      ApplyArgs{n_valid, x, ldx, y, ldy, n, (int)C, save_mean, save_invstd,
+                                weight, bias, relu});
 }
 
 // Projection + BatchNorm (+ ReLU) forward (see k_proj_bn_fwd): one launch where
@@ -2035,13 +2023,13 @@ extern "C" int hlhgat_proj_bn_fwd(int nblocks, const float* const* A, const int6
                                   float* save_invstd, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
   HLH_CHECK_ARG(nblocks >= 1 && nblocks <= MAXB, "proj_bn_fwd: nblocks=%d", nblocks);
-  HLH_CHECK_ARG(M >= 1 && N >= 1 && N < (1 << 20) && ldx >= N && ldy >= N,
-                "proj_bn_fwd: bad sizes M=%lld N=%lld", (long long)M, (long long)N);
   HLH_CHECK_ARG(x && y && save_mean && save_invstd, "proj_bn_fwd: NULL pointer");
   HLH_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
                 "proj_bn_fwd: running_mean/var must both be given or both NULL");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(M, N),
-                "proj_bn_fwd: workspace too small");
+  BnCall c;  // hlhgat_bn_fwd_train's over (x, y): the split apply, the shared checks
+  if (int rc = BnCall::forward(c, "proj_bn_fwd", M, N, {{x, ldx}, {y, ldy}},
+                               {workspace, workspace_bytes, true}))
+    return rc;
   bool vec = true;
   int64_t ktot = 0;
   for (int b = 0; b < nblocks; ++b) {
@@ -2079,30 +2067,10 @@ extern "C" int hlhgat_proj_bn_fwd(int nblocks, const float* const* A, const int6
     a.g.ldw[b] = ldw[b];
     a.g.kb[b] = (int)kb[b];
   }
-  BnWs w = carve(workspace, M, N);
-  StatsArgs& s = a.s;
-  s.nvalid = n_valid;
-  s.n = M;
-  s.C = (int)N;
-  s.part = w.part;
-  s.gpart = w.gpart;
-  s.count = w.count;
-  s.slots = w.slots;
-  s.weight = bn_weight;
-  s.bias = bn_bias;
-  s.running_mean = running_mean;
-  s.running_var = running_var;
-  s.nbt = num_batches_tracked;
-  s.momentum = momentum;
-  s.eps = eps;
-  s.save_mean = save_mean;
-  s.save_invstd = save_invstd;
-  s.out = y;
-  s.ldo = ldy;
-  s.relu = relu;
-  s.wait_us = g_wait_us;
-  s.err = hlhgat::device_error_word();
-  HLH_CHECK_ARG(s.err, "proj_bn_fwd: no device error word (%s)", hlhgat_last_error());
+  a.s = stats_args(c, x, ldx, n_valid);
+  set_fwd_final(a.s, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked,
+                momentum, eps, save_mean, save_invstd);
+  if (int rc = set_one_launch_out(a.s, "proj_bn_fwd", y, ldy, relu)) return rc;
   // algorithmic: A read once, x and y written once; flops of the projection
   const double flops = 2.0 * (double)M * (double)N * (double)ktot;
   const double bytes = 4.0 * (double)M * ((double)ktot + 2.0 * (double)N);
@@ -2112,25 +2080,14 @@ extern "C" int hlhgat_proj_bn_fwd(int nblocks, const float* const* A, const int6
   if (g_pb_stamps && g_pb_stamps_words >= (int64_t)gx * gy * 8) a.stamps = g_pb_stamps;
   {
     ProfScope prof(HLHGAT_PROF_PROJ_BN, st, bytes, flops);
-    if (a.stamps)
-      launch(k_proj_bn_fwd<true>, dim3(gx, gy), dim3(kThreads), 0, st, &prof, a);
-    else
-      launch(k_proj_bn_fwd<false>, dim3(gx, gy), dim3(kThreads), 0, st, &prof, a);
+    launch(a.stamps ? k_proj_bn_fwd<true> : k_proj_bn_fwd<false>, dim3(gx, gy), dim3(kThreads), 0,
+           st, &prof, a);
   }
   HLH_CHECK_LAUNCH();
-  if (split) {
-    const bool vec2 = bn_vec_ok(N, {ldx, ldy}, {x, y});
-    const BnLayout L = bn_layout(M, N, vec2);
-    ApplyArgs p{n_valid, x, ldx, y, ldy, M, (int)N, save_mean, save_invstd, bn_weight, bn_bias,
-                relu, L.tpr, L.rp};
-    dim3 g2(apply_grid_x(M, L.rp), L.tiles);
-    if (vec2)
-      launch(k_bn_apply<4>, g2, dim3(kThreads), 0, st, nullptr, p);
-    else
-      launch(k_bn_apply<1>, g2, dim3(kThreads), 0, st, nullptr, p);
-    HLH_CHECK_LAUNCH();
-  }
-  return HLHGAT_OK;
+  if (!split) return HLHGAT_OK;
+  return launch_apply(c, st,
+                      ApplyArgs{n_valid, x, ldx, y, ldy, M, (int)N, save_mean, save_invstd,
+                                bn_weight, bn_bias, relu});
 }
 
 extern "C" int hlhgat_set_proj_bn_split(int on) {
@@ -2157,57 +2114,31 @@ extern "C" int hlhgat_bn_bwd_train(const float* x, int64_t ldx, const float* y,
                                    float* dx, int64_t lddx, float* dweight,
                                    float* dbias, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && ldx >= C && lddy >= C && lddx >= C && (!y || ldy >= C),
-                "bn_bwd_train: bad sizes");
   HLH_CHECK_ARG(x && dy && dx && save_mean && save_invstd, "bn_bwd_train: NULL pointer");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_bwd_train: workspace too small");
-  const bool vec = bn_vec_ok(C, {ldx, lddy, lddx, y ? ldy : 4}, {x, y, dy, dx});
-  BnLayout L = bn_layout(n, C, vec, bn_bwd_min_parts());
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_bwd_train: C too large");
-  BnWs w = carve(workspace, n, C);
-  StatsArgs s = stats_args(L, w, x, ldx, n, n_valid, C);
-  s.flat_max = bn_bwd_flat_max();
-  s.y = y;
-  s.ldy = ldy;
-  s.dy = dy;
-  s.lddy = lddy;
-  s.weight = weight;
-  s.save_mean = const_cast<float*>(save_mean);
-  s.save_invstd = const_cast<float*>(save_invstd);
-  s.coef = w.coef;
-  s.dweight = dweight;
-  s.dbias = dbias;
+  BnCall c;
+  if (int rc = BnCall::backward(c, "bn_bwd_train", n, C,
+                                {{x, ldx}, {y, ldy}, {dy, lddy}, {dx, lddx}},
+                                {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
+  set_bwd(s, y, ldy, dy, lddy, weight, save_mean, save_invstd, c.w.coef, dweight, dbias);
   hipStream_t st = as_stream(stream);
-  dim3 g1(L.parts, L.tiles);
-  if (GridFn f = pick_bwd_grid(L, vec)) {  // one launch: reduce, coefficients and dx
-    s.out = dx;
-    s.ldo = lddx;
-    s.wait_us = g_wait_us;
-    HLH_CHECK_ARG(s.err, "bn_bwd_train: no device error word (%s)", hlhgat_last_error());
+  if (GridFn f = pick_grid(c, grid_table<BwdGrid>(), bn_one_launch() && bn_bwd_one_launch_flag(),
+                           kMaxParts)) {  // one launch: reduce, coefficients and dx
+    if (int rc = set_one_launch_out(s, "bn_bwd_train", dx, lddx, 0)) return rc;
     // algorithmic bytes: x, dy (and y) read once, dx written once
     ProfScope prof(HLHGAT_PROF_BN_BWD, st, (y ? 16.0 : 12.0) * (double)n * C, 0.0);
-    launch(f, g1, dim3(kThreads), 0, st, &prof, s);
+    launch(f, c.stats_grid(), dim3(kThreads), 0, st, &prof, s);
     HLH_CHECK_LAUNCH();
     return HLHGAT_OK;
   }
   {  // algorithmic bytes of the reduction: x, dy (and y for the ReLU mask) read once
     ProfScope prof(HLHGAT_PROF_BN_BWD, st, (y ? 12.0 : 8.0) * (double)n * C, 0.0);
-    if (vec)
-      launch_bwd_reduce(true, g1, st, &prof, s);
-    else
-      launch_bwd_reduce(false, g1, st, &prof, s);
+    if (int rc = launch_bwd_reduce(c, st, &prof, s)) return rc;
   }
-  HLH_CHECK_LAUNCH();
-  BwdApplyArgs p{n_valid, x, ldx, y, ldy, dy, lddy, dx, lddx, n, (int)C, w.coef, save_mean,
-                 L.tpr, L.rp};
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_bwd_apply<4>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  else
-    launch(k_bn_bwd_apply<1>, dim3(g2), dim3(kThreads), 0, st, nullptr, p);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_bwd_apply(c, st,
+                          BwdApplyArgs{n_valid, x, ldx, y, ldy, dy, lddy, dx, lddx, n, (int)C,
+                                       c.w.coef, save_mean});
 }
 
 extern "C" int hlhgat_bn_bwd_reduce(const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -2216,36 +2147,16 @@ extern "C" int hlhgat_bn_bwd_reduce(const float* x, int64_t ldx, const float* y,
                                     const float* save_mean, const float* save_invstd,
                                     float* coef, float* dweight, float* dbias, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && ldx >= C && lddy >= C && (!y || ldy >= C),
-                "bn_bwd_reduce: bad sizes");
   HLH_CHECK_ARG(x && dy && coef && save_mean && save_invstd, "bn_bwd_reduce: NULL pointer");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_bwd_reduce: workspace too small");
-  // the layout hlhgat_bn_bwd_train picks for an aligned dx: the same bits
-  const bool vec = bn_vec_ok(C, {ldx, lddy, y ? ldy : 4}, {x, y, dy});
-  BnLayout L = bn_layout(n, C, vec, bn_bwd_min_parts());
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_bwd_reduce: C too large");
-  BnWs w = carve(workspace, n, C);
-  StatsArgs s = stats_args(L, w, x, ldx, n, n_valid, C);
-  s.flat_max = bn_bwd_flat_max();
-  s.y = y;
-  s.ldy = ldy;
-  s.dy = dy;
-  s.lddy = lddy;
-  s.weight = weight;
-  s.save_mean = const_cast<float*>(save_mean);
-  s.save_invstd = const_cast<float*>(save_invstd);
-  s.coef = coef;
-  s.dweight = dweight;
-  s.dbias = dbias;
+  BnCall c;  // hlhgat_bn_bwd_train's for an aligned dx
+  if (int rc = BnCall::backward(c, "bn_bwd_reduce", n, C, {{x, ldx}, {y, ldy}, {dy, lddy}},
+                                {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
+  set_bwd(s, y, ldy, dy, lddy, weight, save_mean, save_invstd, coef, dweight, dbias);
   hipStream_t st = as_stream(stream);
   ProfScope prof(HLHGAT_PROF_BN_BWD, st, (y ? 12.0 : 8.0) * (double)n * C, 0.0);
-  if (vec)
-    launch_bwd_reduce(true, dim3(L.parts, L.tiles), st, &prof, s);
-  else
-    launch_bwd_reduce(false, dim3(L.parts, L.tiles), st, &prof, s);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_bwd_reduce(c, st, &prof, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -2256,24 +2167,14 @@ extern "C" int64_t hlhgat_bn_sums_len(int64_t C) { return C > 0 ? 2 * C + 1 : 0;
 extern "C" int hlhgat_bn_sums_fwd(const float* x, int64_t ldx, const float* y, int64_t ldy,
                                   int64_t n, const int32_t* n_valid, int64_t C, double* sums,
                                   void* workspace, int64_t workspace_bytes, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C && (!y || ldy >= C),
-                "bn_sums_fwd: bad sizes n=%lld C=%lld", (long long)n, (long long)C);
   HLH_CHECK_ARG(x && sums, "bn_sums_fwd: NULL pointer");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_sums_fwd: workspace too small");
-  // the layout (hence the partial order) of hlhgat_bn_fwd_train over (x, y)
-  const bool vec = bn_vec_ok(C, {ldx, y ? ldy : 4}, {x, y});
-  const BnLayout L = bn_layout(n, C, vec);
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_sums_fwd: C too large");
-  StatsArgs s = stats_args(L, carve(workspace, n, C), x, ldx, n, n_valid, C);
+  BnCall c;  // hlhgat_bn_fwd_train's, hence its partial order
+  if (int rc = BnCall::forward(c, "bn_sums_fwd", n, C, {{x, ldx}, {y, ldy}},
+                               {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
   s.sums_out = sums;
-  dim3 g1(L.parts, L.tiles);
-  if (vec)
-    launch(k_bn_stats<4>, dim3(g1), dim3(kThreads), 0, as_stream(stream), nullptr, s);
-  else
-    launch(k_bn_stats<1>, dim3(g1), dim3(kThreads), 0, as_stream(stream), nullptr, s);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_stats(c, as_stream(stream), s);
 }
 
 extern "C" int hlhgat_bn_sync_fwd_apply(const float* x, int64_t ldx, int64_t n,
@@ -2284,14 +2185,12 @@ extern "C" int hlhgat_bn_sync_fwd_apply(const float* x, int64_t ldx, int64_t n,
                                         float momentum, float eps, int relu, float* y,
                                         int64_t ldy, float* save_mean, float* save_invstd,
                                         void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && C < (1 << 20) && ldx >= C && ldy >= C && world >= 1,
-                "bn_sync_fwd_apply: bad sizes n=%lld C=%lld world=%d", (long long)n,
-                (long long)C, world);
+  HLH_CHECK_ARG(world >= 1, "bn_sync_fwd_apply: bad sizes world=%d", world);
   HLH_CHECK_ARG(x && y && gathered && save_mean && save_invstd, "bn_sync_fwd_apply: NULL pointer");
   HLH_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr),
                 "bn_sync_fwd_apply: running_mean/var must both be given or both NULL");
-  const bool vec = bn_vec_ok(C, {ldx, ldy}, {x, y});
-  const BnLayout L = bn_layout(n, C, vec);
+  BnCall c;
+  if (int rc = BnCall::forward(c, "bn_sync_fwd_apply", n, C, {{x, ldx}, {y, ldy}})) return rc;
   SyncArgs a{};
   a.nvalid = n_valid;
   a.x = x;
@@ -2300,8 +2199,8 @@ extern "C" int hlhgat_bn_sync_fwd_apply(const float* x, int64_t ldx, int64_t n,
   a.ldo = ldy;
   a.n = n;
   a.C = (int)C;
-  a.tpr = L.tpr;
-  a.rp = L.rp;
+  a.tpr = c.L.tpr;
+  a.rp = c.L.rp;
   a.gathered = gathered;
   a.world = world;
   a.weight = weight;
@@ -2314,13 +2213,8 @@ extern "C" int hlhgat_bn_sync_fwd_apply(const float* x, int64_t ldx, int64_t n,
   a.save_mean = save_mean;
   a.save_invstd = save_invstd;
   a.relu = relu;
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_sync_apply<4>, dim3(g2), dim3(kThreads), 0, as_stream(stream), nullptr, a);
-  else
-    launch(k_bn_sync_apply<1>, dim3(g2), dim3(kThreads), 0, as_stream(stream), nullptr, a);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_v(c.vec, k_bn_sync_apply<4>, k_bn_sync_apply<1>, c.apply_grid(),
+                  as_stream(stream), nullptr, a);
 }
 
 extern "C" int hlhgat_bn_sums_bwd(const float* x, int64_t ldx, const float* y, int64_t ldy,
@@ -2329,35 +2223,16 @@ extern "C" int hlhgat_bn_sums_bwd(const float* x, int64_t ldx, const float* y, i
                                   const float* save_mean, const float* save_invstd,
                                   double* sums, float* dweight, float* dbias, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && ldx >= C && lddy >= C && (!y || ldy >= C) &&
-                    (!dx_layout || lddx >= C),
-                "bn_sums_bwd: bad sizes");
   HLH_CHECK_ARG(x && dy && sums && save_mean && save_invstd, "bn_sums_bwd: NULL pointer");
-  HLH_CHECK_ARG(workspace && workspace_bytes >= (int64_t)bn_ws_bytes(n, C),
-                "bn_sums_bwd: workspace too small");
-  // the layout of hlhgat_bn_bwd_train over (x, y, dy, dx)
-  const bool vec = bn_vec_ok(C, {ldx, lddy, dx_layout ? lddx : 4, y ? ldy : 4},
-                             {x, y, dy, dx_layout});
-  const BnLayout L = bn_layout(n, C, vec, bn_bwd_min_parts());
-  HLH_CHECK_ARG(L.tiles <= kMaxTiles, "bn_sums_bwd: C too large");
-  StatsArgs s = stats_args(L, carve(workspace, n, C), x, ldx, n, n_valid, C);
-  s.flat_max = bn_bwd_flat_max();  // the plain backward's partitions and order
-  s.y = y;
-  s.ldy = ldy;
-  s.dy = dy;
-  s.lddy = lddy;
-  s.save_mean = const_cast<float*>(save_mean);
-  s.save_invstd = const_cast<float*>(save_invstd);
-  s.dweight = dweight;
-  s.dbias = dbias;
+  BnCall c;  // hlhgat_bn_bwd_train's: the plain backward's partitions and order
+  if (int rc = BnCall::backward(c, "bn_sums_bwd", n, C,
+                                {{x, ldx}, {y, ldy}, {dy, lddy}, {dx_layout, lddx}},
+                                {workspace, workspace_bytes, true}))
+    return rc;
+  StatsArgs s = stats_args(c, x, ldx, n_valid);
+  set_bwd(s, y, ldy, dy, lddy, nullptr, save_mean, save_invstd, nullptr, dweight, dbias);
   s.sums_out = sums;
-  dim3 g1(L.parts, L.tiles);
-  if (vec)
-    launch_bwd_reduce(true, dim3(g1), as_stream(stream), nullptr, s);
-  else
-    launch_bwd_reduce(false, dim3(g1), as_stream(stream), nullptr, s);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_bwd_reduce(c, as_stream(stream), nullptr, s);
 }
 
 extern "C" int hlhgat_bn_sync_bwd_apply(const float* x, int64_t ldx, const float* y,
@@ -2366,13 +2241,13 @@ extern "C" int hlhgat_bn_sync_bwd_apply(const float* x, int64_t ldx, const float
                                         const float* save_mean, const float* save_invstd,
                                         const double* gathered, int world, float* dx,
                                         int64_t lddx, void* stream) {
-  HLH_CHECK_ARG(n >= 1 && C >= 1 && ldx >= C && lddy >= C && lddx >= C && (!y || ldy >= C) &&
-                    world >= 1,
-                "bn_sync_bwd_apply: bad sizes");
+  HLH_CHECK_ARG(world >= 1, "bn_sync_bwd_apply: bad sizes world=%d", world);
   HLH_CHECK_ARG(x && dy && dx && gathered && save_mean && save_invstd,
                 "bn_sync_bwd_apply: NULL pointer");
-  const bool vec = bn_vec_ok(C, {ldx, lddy, lddx, y ? ldy : 4}, {x, y, dy, dx});
-  const BnLayout L = bn_layout(n, C, vec);
+  BnCall c;
+  if (int rc = BnCall::backward(c, "bn_sync_bwd_apply", n, C,
+                                {{x, ldx}, {y, ldy}, {dy, lddy}, {dx, lddx}}))
+    return rc;
   SyncArgs a{};
   a.nvalid = n_valid;
   a.x = x;
@@ -2385,20 +2260,15 @@ extern "C" int hlhgat_bn_sync_bwd_apply(const float* x, int64_t ldx, const float
   a.ldo = lddx;
   a.n = n;
   a.C = (int)C;
-  a.tpr = L.tpr;
-  a.rp = L.rp;
+  a.tpr = c.L.tpr;
+  a.rp = c.L.rp;
   a.gathered = gathered;
   a.world = world;
   a.weight = weight;
   a.save_mean = const_cast<float*>(save_mean);
   a.save_invstd = const_cast<float*>(save_invstd);
-  dim3 g2(apply_grid_x(n, L.rp), L.tiles);
-  if (vec)
-    launch(k_bn_sync_bwd_apply<4>, dim3(g2), dim3(kThreads), 0, as_stream(stream), nullptr, a);
-  else
-    launch(k_bn_sync_bwd_apply<1>, dim3(g2), dim3(kThreads), 0, as_stream(stream), nullptr, a);
-  HLH_CHECK_LAUNCH();
-  return HLHGAT_OK;
+  return launch_v(c.vec, k_bn_sync_bwd_apply<4>, k_bn_sync_bwd_apply<1>, c.apply_grid(),
+                  as_stream(stream), nullptr, a);
 }
 
 extern "C" int hlhgat_set_bn_one_launch(int on) {

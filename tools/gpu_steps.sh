@@ -143,21 +143,9 @@ for s in "$@"; do
            step abload_$d 400 python3 bench.py --full --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --loader-depth $d
            python3 -c "import json,sys; r=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{\"metric')][-1]; L=r['loader']; print('depth', sys.argv[2], r['ms_per_step'], L['loader_fed']['ms_per_step'], round(r['ms_per_step']/L['loader_fed']['ms_per_step'],3), L['loader_fed']['host_ms_per_step'])" gpurun_out/${TAG}_abload_$d.log $d >> gpurun_out/${TAG}_abload.txt || true
          done ;;
-    abbn) for r in 1 2; do for v in 128 64 256 512; do
-           HLHGAT_BN_BWD_PARTS=$v step abbn_${v}_$r 300 python3 bench.py --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --no-loader --steps 30
-           grep -o '"ms_per_step": [0-9.]*' gpurun_out/${TAG}_abbn_${v}_$r.log | sed "s/^/bwd_parts=$v run $r /" >> gpurun_out/${TAG}_abbn.txt || true
-         done; done ;;
     abws) for r in 1 2; do for v in 360 180 240 540; do
            HLHGAT_WSPLIT_TARGET=$v step abws_${v}_$r 300 python3 bench.py --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --no-loader --steps 30
            grep -o '"ms_per_step": [0-9.]*' gpurun_out/${TAG}_abws_${v}_$r.log | sed "s/^/wsplit_target=$v run $r /" >> gpurun_out/${TAG}_abws.txt || true
-         done; done ;;
-    abbn2) for r in 1 2; do for v in 128:256 128:16 512:256 256:16 512:16; do pp=${v%%:*}; fm=${v##*:}
-           HLHGAT_BN_BWD_PARTS=$pp HLHGAT_BN_BWD_FLAT_MAX=$fm step abbn2_${pp}_${fm}_$r 300 python3 bench.py --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --no-loader --steps 30
-           grep -o '"ms_per_step": [0-9.]*' gpurun_out/${TAG}_abbn2_${pp}_${fm}_$r.log | sed "s/^/parts=$pp flat_max=$fm run $r /" >> gpurun_out/${TAG}_abbn2.txt || true
-         done; done ;;
-    abnew) for r in 1 2 3; do for v in 360:256 240:16; do t=${v%%:*}; fm=${v##*:}
-           HLHGAT_WSPLIT_TARGET=$t HLHGAT_BN_BWD_FLAT_MAX=$fm step abnew_${t}_${fm}_$r 300 python3 bench.py --no-cfg5 --no-heads --no-cpu-baseline --no-parity-check --no-replay-census --no-loader --steps 30
-           grep -o '"ms_per_step": [0-9.]*' gpurun_out/${TAG}_abnew_${t}_${fm}_$r.log | sed "s/^/wsplit=$t flat_max=$fm run $r /" >> gpurun_out/${TAG}_abnew.txt || true
          done; done ;;
     abload9) for r in 1 2; do for v in base host hostsl4 devsl4; do
            case $v in base) E=""; A="";; host) E="HLHGAT_STAGE_WAIT=host"; A="";; hostsl4) E="HLHGAT_STAGE_WAIT=host"; A="--loader-slots 4";; devsl4) E=""; A="--loader-slots 4";; esac
