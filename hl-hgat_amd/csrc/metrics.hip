@@ -19,6 +19,13 @@
 //               group ends (tp of the previous group), carried across chunks.
 //               Each thread adds the fp64 terms of its rows in row order; one
 //               fixed LDS tree sums the 256 partial sums.  No atomics.
+//
+// The meters of the other test() loops (hlhgat.metrics), each one launch:
+//   k_collect_rows        append rows at a device-side cursor, then advance it
+//   k_f1_per_graph        BinaryF1Score of every graph of a batch
+//   k_argmax_correct      the argmax(out, 1) == y count
+//   k_regression_summary  sums, means, deviations and correlation, in fp64
+// Integer counts or a fixed summation order, no atomics, no synchronisation.
 #include "common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -197,6 +204,202 @@ __global__ __launch_bounds__(kThreads) void k_ap_walk(const uint64_t* __restrict
   if (tid == 0) ap[c] = sh_sum[0];
 }
 
+// Raise `bit` in the device error word: a load and a store (k_ap_keys).
+__device__ __forceinline__ void raise_error(unsigned* err, unsigned bit) {
+  if (!err) return;
+  const unsigned old = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(err, old | bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Sum of v over the 256 threads of the block, in every thread (integers: any
+// order gives the same result).  sh holds kWaves ints; two barriers.
+__device__ __forceinline__ int block_sum_int(int v, int* sh) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+  __syncthreads();  // sh free again
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) t += sh[w];
+  return t;
+}
+
+// ---- collect_rows -----------------------------------------------------------
+// One workgroup: the appends of an evaluation loop are a batch's outputs (a few
+// thousand floats at most), and one workgroup can advance the cursor after its
+// own copy behind a barrier, with no protocol between workgroups.
+__global__ __launch_bounds__(kThreads) void k_collect_rows(const float* __restrict__ x,
+                                                           int64_t ldx, int64_t n, int64_t d,
+                                                           float* __restrict__ buf,
+                                                           int64_t capacity, int64_t* cursor,
+                                                           unsigned* err) {
+  const int64_t cur = *cursor;  // every thread reads it before thread 0 may write it
+  const bool fits = cur >= 0 && cur <= capacity && n <= capacity - cur;
+  if (fits) {
+    float* dst = buf + cur * d;
+    const int64_t total = n * d;
+    if (d == 1) {
+      for (int64_t e = threadIdx.x; e < total; e += kThreads) dst[e] = x[e * ldx];
+    } else {
+      for (int64_t e = threadIdx.x; e < total; e += kThreads) {
+        const int64_t r = e / d;
+        dst[e] = x[r * ldx + (e - r * d)];
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (fits) *cursor = cur + n;
+    else raise_error(err, (unsigned)HLHGAT_DEVERR_METER_FULL);
+  }
+}
+
+// ---- f1_per_graph -----------------------------------------------------------
+// One workgroup per graph, one pass over its rows: the counts under both
+// formatting rules (raw threshold, sigmoid threshold) and the number of logits
+// outside [0, 1], which picks the rule once the block knows it.
+__global__ __launch_bounds__(kThreads) void k_f1_per_graph(const float* __restrict__ logit,
+                                                           int64_t ldp,
+                                                           const float* __restrict__ label,
+                                                           int64_t ldy,
+                                                           const int32_t* __restrict__ seg_ptr,
+                                                           int64_t rows, float* __restrict__ f1,
+                                                           unsigned* err) {
+  __shared__ int sh[kWaves];
+  const int g = blockIdx.x;
+  int64_t lo = seg_ptr[g], hi = seg_ptr[g + 1];
+  if (lo < 0) lo = 0;
+  if (hi > rows) hi = rows;  // never past the tensors, whatever seg_ptr holds
+  int outside = 0, pos = 0, tp_raw = 0, pp_raw = 0, tp_sig = 0, pp_sig = 0;
+  bool bad = false;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) {
+    const float p = logit[i * ldp];
+    const float y = label[i * ldy];
+    const bool is_pos = y == 1.0f;
+    if (!is_pos && !(y == 0.0f)) bad = true;
+    outside += !(0.0f <= p && p <= 1.0f);  // a NaN is outside
+    const bool raw = p > 0.5f;
+    const bool sig = __fdiv_rn(1.0f, 1.0f + expf(-p)) > 0.5f;
+    pos += is_pos;
+    pp_raw += raw;
+    tp_raw += raw && is_pos;
+    pp_sig += sig;
+    tp_sig += sig && is_pos;
+  }
+  outside = block_sum_int(outside, sh);
+  pos = block_sum_int(pos, sh);
+  const int tp = block_sum_int(outside ? tp_sig : tp_raw, sh);  // outside: block-uniform
+  const int pp = block_sum_int(outside ? pp_sig : pp_raw, sh);
+  if (bad) raise_error(err, (unsigned)HLHGAT_DEVERR_METRIC_LABEL);
+  if (threadIdx.x == 0) {
+    // 2tp + fp + fn with fp = pp - tp, fn = pos - tp
+    const int64_t den = (int64_t)pp + (int64_t)pos;
+    f1[g] = den > 0 ? __fdiv_rn((float)(2 * (int64_t)tp), (float)den) : 0.0f;
+  }
+}
+
+// ---- argmax_correct ---------------------------------------------------------
+// One workgroup, one thread per row (the batch's graphs: a few hundred rows).
+__global__ __launch_bounds__(kThreads) void k_argmax_correct(const float* __restrict__ x,
+                                                             int64_t ldx, int64_t n, int64_t C,
+                                                             const int64_t* __restrict__ label,
+                                                             int64_t* correct, int64_t* seen,
+                                                             unsigned* err) {
+  __shared__ int sh[kWaves];
+  int hit = 0;
+  bool bad = false;
+  for (int64_t r = threadIdx.x; r < n; r += kThreads) {
+    const float* row = x + r * ldx;
+    float best = row[0];
+    int64_t arg = 0;
+    // torch's CPU rule: the first index of the greatest value, NaN greatest
+    for (int64_t j = 1; j < C && best == best; ++j) {
+      const float v = row[j];
+      if (v > best || v != v) {
+        best = v;
+        arg = j;
+      }
+    }
+    const int64_t y = label[r];
+    if (y < 0 || y >= C) bad = true;
+    hit += y == arg;
+  }
+  hit = block_sum_int(hit, sh);
+  if (bad) raise_error(err, (unsigned)HLHGAT_DEVERR_METRIC_LABEL);
+  if (threadIdx.x == 0) {
+    *correct += hit;
+    if (seen) *seen += n;
+  }
+}
+
+// ---- regression_summary -----------------------------------------------------
+constexpr int kSumThreads = 1024;
+
+// Sums of v[0..3] over the block in one fixed tree; the result in every thread.
+__device__ __forceinline__ void block_sum4(double (&v)[4], double (*sh)[kSumThreads]) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // sh free again
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sh[q][tid] = v[q];
+  __syncthreads();
+  for (int w = kSumThreads / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sh[q][tid] = sh[q][tid] + sh[q][tid + w];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = sh[q][0];
+}
+
+// One workgroup, two passes in fp64: N is a dataset's size (1e4 - 1e5 values,
+// 100 per thread), so the launch is latency-bound either way and a single
+// workgroup keeps the summation order a function of N alone.
+__global__ __launch_bounds__(kSumThreads) void k_regression_summary(
+    const float* __restrict__ pred, const float* __restrict__ y, const int64_t* __restrict__ count,
+    int64_t capacity, double* __restrict__ out) {
+  __shared__ double sh[4][kSumThreads];
+  const int tid = threadIdx.x;
+  int64_t N = *count;
+  if (N < 0) N = 0;
+  if (N > capacity) N = capacity;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double dn = (double)N;
+  double s1[4] = {0.0, 0.0, 0.0, 0.0};  // sum p, sum y, sum |d|, sum d^2
+  for (int64_t i = tid; i < N; i += kSumThreads) {
+    const double p = (double)pred[i], t = (double)y[i];
+    const double d = p - t;
+    s1[0] += p;
+    s1[1] += t;
+    s1[2] += fabs(d);
+    s1[3] += d * d;
+  }
+  block_sum4(s1, sh);
+  const double mp = N > 0 ? s1[0] / dn : nan, my = N > 0 ? s1[1] / dn : nan;
+  double s2[4] = {0.0, 0.0, 0.0, 0.0};  // centred: sum a^2, sum b^2, sum a b, unused
+  for (int64_t i = tid; i < N; i += kSumThreads) {
+    const double a = (double)pred[i] - mp, b = (double)y[i] - my;
+    s2[0] += a * a;
+    s2[1] += b * b;
+    s2[2] += a * b;
+  }
+  block_sum4(s2, sh);
+  if (tid == 0) {
+    const double sdp = N > 1 ? sqrt(s2[0] / (dn - 1.0)) : nan;
+    const double sdy = N > 1 ? sqrt(s2[1] / (dn - 1.0)) : nan;
+    out[0] = dn;
+    out[1] = s1[2];
+    out[2] = s1[3];
+    out[3] = mp;
+    out[4] = my;
+    out[5] = sdp;
+    out[6] = sdy;
+    out[7] = N > 1 ? s2[2] / (dn * (sdp * sdy)) : nan;  // a zero deviation: 0 / 0
+  }
+}
+
 int bits_of(uint64_t v) {  // bits needed to represent the value v (at least 1)
   int b = 1;
   while (b < 64 && (v >> b) > 0) ++b;
@@ -300,6 +503,78 @@ extern "C" int hlhgat_average_precision(const float* pred, int64_t ldp, const fl
                                                    vals_out, (int)items, 0, key_bits(C), s));
   launch(k_ap_walk, dim3((unsigned)C), dim3(kThreads), 0, s, nullptr, (const uint64_t*)keys_out,
          (const unsigned char*)vals_out, n, ap, counts);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_collect_rows(const float* x, int64_t ldx, int64_t n, int64_t d, float* buf,
+                                   int64_t capacity, int64_t* cursor, void* stream) {
+  HLH_CHECK_ARG(n >= 0 && capacity >= 0, "collect_rows: n=%lld or capacity=%lld < 0",
+                (long long)n, (long long)capacity);
+  HLH_CHECK_ARG(d > 0, "collect_rows: d=%lld must be positive", (long long)d);
+  if (n == 0) return HLHGAT_OK;
+  HLH_CHECK_ARG(x && buf && cursor, "collect_rows: NULL pointer");
+  HLH_CHECK_ARG(ldx >= d || n == 1, "collect_rows: row stride %lld below d=%lld", (long long)ldx,
+                (long long)d);
+  HLH_CHECK_ARG(n <= INT64_MAX / d && capacity <= INT64_MAX / d / 4,
+                "collect_rows: n * d or capacity * d out of range");
+  HLH_CHECK_ARG(aligned8(cursor), "collect_rows: cursor must be 8-byte aligned");
+  unsigned* err = device_error_word();
+  HLH_CHECK_ARG(err, "collect_rows: %s", hlhgat_last_error());
+  launch(k_collect_rows, dim3(1), dim3(kThreads), 0, as_stream(stream), nullptr, x, ldx, n, d, buf,
+         capacity, cursor, err);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_f1_per_graph(const float* logit, int64_t ldp, const float* label,
+                                   int64_t ldy, const int32_t* seg_ptr, int64_t n_graphs,
+                                   int64_t rows, float* f1, void* stream) {
+  HLH_CHECK_ARG(n_graphs >= 0 && rows >= 0, "f1_per_graph: n_graphs=%lld or rows=%lld < 0",
+                (long long)n_graphs, (long long)rows);
+  HLH_CHECK_ARG(n_graphs < INT32_MAX && rows <= INT32_MAX,
+                "f1_per_graph: n_graphs or rows out of int32 range");
+  if (n_graphs == 0) return HLHGAT_OK;
+  HLH_CHECK_ARG(seg_ptr && f1, "f1_per_graph: NULL seg_ptr or output pointer");
+  HLH_CHECK_ARG(rows == 0 || (logit && label), "f1_per_graph: NULL input pointer");
+  HLH_CHECK_ARG(ldp >= 1 && ldy >= 1, "f1_per_graph: stride below 1");
+  unsigned* err = device_error_word();
+  HLH_CHECK_ARG(err, "f1_per_graph: %s", hlhgat_last_error());
+  launch(k_f1_per_graph, dim3((unsigned)n_graphs), dim3(kThreads), 0, as_stream(stream), nullptr,
+         logit, ldp, label, ldy, seg_ptr, rows, f1, err);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_argmax_correct(const float* x, int64_t ldx, int64_t n, int64_t C,
+                                     const int64_t* label, int64_t* correct, int64_t* seen,
+                                     void* stream) {
+  HLH_CHECK_ARG(n >= 0, "argmax_correct: n=%lld < 0", (long long)n);
+  HLH_CHECK_ARG(C > 0, "argmax_correct: C=%lld must be positive", (long long)C);
+  if (n == 0) return HLHGAT_OK;
+  HLH_CHECK_ARG(x && label && correct, "argmax_correct: NULL pointer");
+  HLH_CHECK_ARG(ldx >= C || n == 1, "argmax_correct: row stride %lld below C=%lld",
+                (long long)ldx, (long long)C);
+  HLH_CHECK_ARG(n <= INT32_MAX, "argmax_correct: n out of int32 range");
+  HLH_CHECK_ARG(aligned8(correct) && aligned8(seen) && aligned8(label),
+                "argmax_correct: int64 pointers must be 8-byte aligned");
+  unsigned* err = device_error_word();
+  HLH_CHECK_ARG(err, "argmax_correct: %s", hlhgat_last_error());
+  launch(k_argmax_correct, dim3(1), dim3(kThreads), 0, as_stream(stream), nullptr, x, ldx, n, C,
+         label, correct, seen, err);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_regression_summary(const float* pred, const float* y, const int64_t* count,
+                                         int64_t capacity, double* out, void* stream) {
+  HLH_CHECK_ARG(capacity >= 0, "regression_summary: capacity=%lld < 0", (long long)capacity);
+  HLH_CHECK_ARG(count && out, "regression_summary: NULL count or output pointer");
+  HLH_CHECK_ARG(capacity == 0 || (pred && y), "regression_summary: NULL input pointer");
+  HLH_CHECK_ARG(aligned8(count) && aligned8(out),
+                "regression_summary: count and out must be 8-byte aligned");
+  launch(k_regression_summary, dim3(1), dim3(kSumThreads), 0, as_stream(stream), nullptr, pred, y,
+         count, capacity, out);
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }

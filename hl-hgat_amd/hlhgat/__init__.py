@@ -21,7 +21,8 @@ from .hodge_st_model import (HL_HGAT_attpool, HL_HGCNN_CIFAR10SP_dense_int3_attp
 # the library class of that name there (hodge_st_model's)
 from .main_pepfunc import HL_HGCNN_pepfunc_dense_int3_attpool  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
-from .metrics import eval_ap  # noqa: F401,E402
+from .metrics import (AccuracyMeter, Collector, F1Meter, RegressionMeter,  # noqa: F401,E402
+                      eval_ap)
 from .nn import (BatchNorm, CrossEntropyLoss, FocalLoss, Linear,  # noqa: F401,E402
                  MaskedBCEWithLogitsLoss, Sequential, global_mean_pool)
 

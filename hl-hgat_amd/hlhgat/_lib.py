@@ -155,6 +155,10 @@ SIGNATURES = {
     "hlhgat_average_precision_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "hlhgat_average_precision": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp,
                                          c_vp, c_sz, c_vp]),
+    "hlhgat_collect_rows": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "hlhgat_f1_per_graph": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "hlhgat_argmax_correct": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "hlhgat_regression_summary": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hlhgat_bce_logits_fwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "hlhgat_bce_logits_bwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_l1_loss_fwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -221,6 +225,7 @@ DEVERR_BN_STATE = 1
 DEVERR_HODGE_SIZE = 2
 DEVERR_LABEL = 4
 DEVERR_METRIC_LABEL = 8
+DEVERR_METER_FULL = 16
 LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
 CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
 LOSS_ONE_LAUNCH_MAX = 16384  # up to here the loss forwards need no workspace

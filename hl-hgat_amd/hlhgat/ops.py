@@ -33,6 +33,7 @@ __all__ = [
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
     "bce_logits_loss", "cross_entropy", "average_precision",
+    "collect_rows", "f1_per_graph", "argmax_correct", "regression_summary",
     "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
@@ -2606,6 +2607,139 @@ def average_precision(pred: torch.Tensor, label: torch.Tensor):
     return ap, counts
 
 
+def _req_i64_scalar(t: torch.Tensor, name: str, like: torch.Tensor) -> None:
+    _req_dev(t, name, torch.int64)
+    if t.numel() != 1 or t.device != like.device:
+        raise RuntimeError(f"hlhgat: {name} must hold one int64 on {like.device}")
+
+
+def collect_rows(x: torch.Tensor, buf: torch.Tensor, cursor: torch.Tensor) -> None:
+    """Append the rows of x ([n, d], or [n] when buf is [capacity, 1]) to buf
+    [capacity, d] at row ``cursor`` (one int64 on the device) and advance the
+    cursor on the device (hlhgat_collect_rows): the device-side
+    ``y_pred.extend(out)``.  Rows that do not fit are not written, the cursor
+    stays and the device error word is raised.  A strided x (unit column
+    stride) is read in place.  No host synchronisation: the call captures, and
+    a replay appends behind the previous replay's rows."""
+    _req_dev(x, "x")
+    _req_dev(buf, "buf")
+    if buf.dim() != 2 or not buf.is_contiguous() or buf.device != x.device or buf.size(1) < 1:
+        raise RuntimeError(f"hlhgat: collect_rows: buf must be contiguous [capacity, d >= 1] on "
+                           f"{x.device}, got {tuple(buf.shape)}")
+    _req_i64_scalar(cursor, "cursor", x)
+    cap, d = buf.shape
+    x = x.detach()
+    if x.dim() == 1 and d == 1:
+        n, ld = x.size(0), (x.stride(0) if x.size(0) > 1 else 1)
+        if ld < 1:
+            x, ld = x.contiguous(), 1
+    else:
+        if x.dim() != 2 or x.size(1) != d:
+            raise RuntimeError(f"hlhgat: collect_rows: x {tuple(x.shape)} does not match buf "
+                               f"[{cap}, {d}]")
+        x = _rows2d(x, "x")
+        n, ld = x.size(0), _ld(x)
+    check(LIB.hlhgat_collect_rows(x.data_ptr(), ld, n, d, buf.data_ptr(), cap, cursor.data_ptr(),
+                                  _stream(x)), "collect_rows")
+
+
+def _vec_ld(t: torch.Tensor, name: str):
+    """A [E] or [E, 1] tensor as (tensor, element stride >= 1)."""
+    if t.dim() == 2 and t.size(1) == 1:
+        t = t[:, 0]
+    if t.dim() != 1:
+        raise RuntimeError(f"hlhgat: {name} must be [E] or [E, 1] (got {tuple(t.shape)})")
+    if t.size(0) > 1 and t.stride(0) < 1:
+        t = t.contiguous()
+    return t, (t.stride(0) if t.size(0) > 1 else 1)
+
+
+def f1_per_graph(logits: torch.Tensor, label: torch.Tensor, seg_ptr: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f1 [G] fp32: torchmetrics' BinaryF1Score() (threshold 0.5) of every
+    graph of a batch in one launch (hlhgat_f1_per_graph), the body of the TSP
+    test() loop (main_TSP...:344-347).  logits / label: [E] or [E, 1] fp32 (a
+    column of a wider tensor is read in place); seg_ptr: int32 [G + 1] row
+    offsets, rows from seg_ptr[G] on (padding) belong to no graph.  Per graph:
+    if every logit lies in [0, 1] the prediction is ``p > 0.5``, otherwise
+    ``sigmoid(p) > 0.5`` (torchmetrics' formatting rule); f1 = 2tp / (2tp + fp
+    + fn), 0 for 0 / 0.  A label other than 0 or 1 counts as a negative and
+    raises the device error word.  No host synchronisation."""
+    _req_dev(logits, "logits")
+    _req_dev(label, "label")
+    _req_dev(seg_ptr, "seg_ptr", torch.int32)
+    x, ldp = _vec_ld(logits.detach(), "logits")
+    y, ldy = _vec_ld(label.detach(), "label")
+    if x.size(0) != y.size(0) or y.device != x.device or seg_ptr.device != x.device or \
+            seg_ptr.dim() != 1 or seg_ptr.numel() < 1 or not seg_ptr.is_contiguous():
+        raise RuntimeError(f"hlhgat: f1_per_graph wants logits and label [E] and contiguous "
+                           f"seg_ptr [G + 1] on one device, got {tuple(logits.shape)}, "
+                           f"{tuple(label.shape)}, {tuple(seg_ptr.shape)}")
+    G = seg_ptr.numel() - 1
+    if out is None:
+        out = torch.empty(G, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.device != x.device or out.numel() != G or \
+            not out.is_contiguous():
+        raise RuntimeError(f"hlhgat: f1_per_graph: out must be contiguous fp32 [{G}] on {x.device}")
+    check(LIB.hlhgat_f1_per_graph(x.data_ptr(), ldp, y.data_ptr(), ldy, seg_ptr.data_ptr(), G,
+                                  x.size(0), out.data_ptr(), _stream(x)), "f1_per_graph")
+    return out
+
+
+def argmax_correct(out: torch.Tensor, label: torch.Tensor, correct: torch.Tensor,
+                   seen: Optional[torch.Tensor] = None) -> None:
+    """correct += the rows of out [n, C] whose argmax is label [n] (int64), and
+    seen += n: ``correct += int((out.argmax(1) == y).sum())`` of the CIFAR
+    loop (main_cifar10SP...:146-161) without the read (hlhgat_argmax_correct).
+    correct / seen: one int64 each on the device.  The argmax is the first
+    index of the greatest value, NaN greatest.  A label outside [0, C) matches
+    nothing and raises the device error word.  No host synchronisation."""
+    _req_dev(out, "out")
+    _req_dev(label, "label", torch.int64)
+    if out.dim() != 2 or out.size(1) < 1 or label.dim() != 1 or label.size(0) != out.size(0) or \
+            label.device != out.device:
+        raise RuntimeError(f"hlhgat: argmax_correct wants out [n, C >= 1] and label [n] on one "
+                           f"device, got {tuple(out.shape)} and {tuple(label.shape)}")
+    _req_i64_scalar(correct, "correct", out)
+    if seen is not None:
+        _req_i64_scalar(seen, "seen", out)
+    x = _rows2d(out.detach(), "out")
+    y = label.contiguous()
+    check(LIB.hlhgat_argmax_correct(x.data_ptr(), _ld(x), x.size(0), x.size(1), y.data_ptr(),
+                                    correct.data_ptr(), _ptr(seen), _stream(x)), "argmax_correct")
+
+
+REGRESSION_FIELDS = ("n", "sum_abs", "sum_sq", "mean_pred", "mean_y", "std_pred", "std_y", "corr")
+
+
+def regression_summary(pred: torch.Tensor, y: torch.Tensor, count: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [8] on the device, in the order of REGRESSION_FIELDS, over the
+    first min(count, capacity) values of the contiguous fp32 buffers pred / y
+    [capacity] (count: one int64 on the device, a collector's cursor), in one
+    launch (hlhgat_regression_summary): N, sum |pred - y|, sum (pred - y)^2,
+    the means, the unbiased standard deviations and the notebook's
+    mean(z(pred) * z(y)).  Two passes in fp64, fixed order.  No host
+    synchronisation."""
+    _req_dev(pred, "pred")
+    _req_dev(y, "y")
+    _req_i64_scalar(count, "count", pred)
+    if pred.numel() != y.numel() or y.device != pred.device or not pred.is_contiguous() or \
+            not y.is_contiguous():
+        raise RuntimeError(f"hlhgat: regression_summary wants contiguous pred and y of one size on "
+                           f"one device, got {tuple(pred.shape)} and {tuple(y.shape)}")
+    if out is None:
+        out = torch.empty(len(REGRESSION_FIELDS), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or out.device != pred.device or \
+            out.numel() != len(REGRESSION_FIELDS) or not out.is_contiguous():
+        raise RuntimeError(f"hlhgat: regression_summary: out must be contiguous fp64 "
+                           f"[{len(REGRESSION_FIELDS)}] on {pred.device}")
+    check(LIB.hlhgat_regression_summary(pred.data_ptr(), y.data_ptr(), count.data_ptr(),
+                                        pred.numel(), out.data_ptr(), _stream(pred)),
+          "regression_summary")
+    return out
+
+
 # ----------------------------------------------------------------------------
 # brain input: z-scored series and functional connectivity (csrc/fc.hip)
 # ----------------------------------------------------------------------------
@@ -2784,6 +2918,9 @@ _DEVERR_TEXT = {
                        "gradient",
     _lib.DEVERR_METRIC_LABEL: "average_precision: a label that is neither NaN, 0 nor 1; it was "
                               "counted as a negative",
+    _lib.DEVERR_METER_FULL: "collect_rows: the rows did not fit the collector's buffer "
+                            "(capacity too small, or no reset() between epochs); none of them "
+                            "was appended",
     _lib.DEVERR_BN_STATE: "BatchNorm: an arrival counter was found beyond its total (the "
                           "workspace was written by something else or shared by concurrent "
                           "launches); that launch's statistics are not trusted",

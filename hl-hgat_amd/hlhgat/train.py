@@ -1050,10 +1050,24 @@ class InferStep:
     shape (the first call of a shape runs eagerly, then captures) and replays
     it; the returned output is the graph's static
     buffer, valid until the next call with a batch of the same shape (clone
-    it to keep it)."""
+    it to keep it).
 
-    def __init__(self, model: torch.nn.Module, graphs: bool = True, max_graphs: int = 32):
+    meter: a callable ``meter(out, batch)`` run inside the forward, under
+    no_grad, on the model's output and the batch it was computed from -- the
+    ``update`` of a hlhgat.metrics meter (F1Meter, AccuracyMeter,
+    RegressionMeter, Collector.append).  Its launches are captured with the
+    forward and replay with it, so an evaluation epoch is replays plus the
+    meter's one ``compute()`` read.  Inside the captured graph ``batch`` is the
+    graph's static copy: the meter must read its labels from ``batch``, not
+    from a tensor it closed over.  The meter's buffers (the meter object
+    itself) must exist before the first call: state allocated during a
+    capture would belong to the graph's pool.  meter=None: exactly the
+    launches of the forward."""
+
+    def __init__(self, model: torch.nn.Module, graphs: bool = True, max_graphs: int = 32,
+                 meter: Optional[Callable] = None):
         self.model = model
+        self.meter = meter
         params = list(model.parameters())
         dev = params[0].device if params else torch.device("cpu")
         self.device = dev
@@ -1069,7 +1083,10 @@ class InferStep:
         self.model.eval()
         try:
             with torch.no_grad():
-                return self.model(batch)
+                out = self.model(batch)
+                if self.meter is not None:
+                    self.meter(out, batch)
+                return out
         finally:
             self.model.train(was)
 
@@ -1103,7 +1120,7 @@ class InferStep:
         return ent
 
     def __call__(self, batch):
-        if ops._ext is not None:
+        if ops._ext is not None and self.device.type == "cuda":  # a CPU model launches nothing
             ops.check_device_errors(sync=False)
         if not self.graphs:
             self.stats["eager"] += 1

@@ -959,6 +959,65 @@ int hlhgat_average_precision(const float* pred, int64_t ldp, const float* label,
                              int64_t n, int64_t C, double* ap, int32_t* counts,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The meters of the reference's other test() loops.  Like the average
+ * precision: no floating-point atomics, a fixed summation order, no host
+ * synchronisation and no allocation, so every call captures into a hipGraph
+ * and an eager and a replayed run give the same bits. */
+
+/* The device-side `y_pred.extend(out)` (OHBM_DEMO.ipynb, train / test cells;
+ * the torch.cat of y_preds / y_trues, main_pepfunc...:201-225): appends the n
+ * rows of x [n, d] (fp32, row stride ldx >= d) to buf [capacity, d] at row
+ * *cursor (int64, device memory), then advances *cursor by n on the device, so
+ * a replayed launch appends behind the previous replay's rows.  If
+ * *cursor + n > capacity nothing is written, the cursor stays, and
+ * HLHGAT_DEVERR_METER_FULL is raised.  n == 0 is a no-op; d >= 1.  One launch
+ * of one workgroup (an append is one batch's outputs). */
+int hlhgat_collect_rows(const float* x, int64_t ldx, int64_t n, int64_t d, float* buf,
+                        int64_t capacity, int64_t* cursor, void* stream);
+
+/* torchmetrics' BinaryF1Score() (threshold 0.5) of every graph of a batch: the
+ * body of the TSP loop (main_TSP_HL_HGCNN_dense_int3_pyr.py:344-347: unbatch,
+ * then one f1() call per graph).  logit [rows] fp32 (element stride ldp),
+ * label [rows] fp32 (element stride ldy), seg_ptr [n_graphs + 1] int32 row
+ * offsets (graph g owns rows seg_ptr[g] .. seg_ptr[g+1]-1; rows from
+ * seg_ptr[n_graphs] on, static-shape padding, belong to no graph; offsets are
+ * clamped to [0, rows]).  Per graph:
+ *   inside = every logit p of the graph has 0 <= p && p <= 1 (a NaN fails);
+ *   pred = p > 0.5f if inside, else 1 / (1 + expf(-p)) > 0.5f in fp32;
+ *   tp, fp, fn = integer counts, label == 1 positive, anything else negative;
+ *   f1[g] = (float)(2 tp) / (float)(2 tp + fp + fn), one correctly rounded
+ *   fp32 division, 0 when the denominator is 0 (a graph of 0 rows too).
+ * A label other than 0 or 1 raises HLHGAT_DEVERR_METRIC_LABEL.  One launch,
+ * one workgroup per graph. */
+int hlhgat_f1_per_graph(const float* logit, int64_t ldp, const float* label, int64_t ldy,
+                        const int32_t* seg_ptr, int64_t n_graphs, int64_t rows, float* f1,
+                        void* stream);
+
+/* The CIFAR loop's accuracy count (main_cifar10SP_HL_HGCNN_dense_int3_attpool
+ * .py:146-161: correct += argmax(out, 1) == y): *correct += the rows of
+ * x [n, C] (fp32, row stride ldx >= C) whose argmax is label[r] (int64), and,
+ * if seen is not NULL, *seen += n; both int64 in device memory, added by one
+ * thread.  The argmax is the first index of the greatest value with NaN
+ * greatest (torch's CPU rule).  A label outside [0, C) matches nothing and
+ * raises HLHGAT_DEVERR_METRIC_LABEL.  One launch of one workgroup; C >= 1. */
+int hlhgat_argmax_correct(const float* x, int64_t ldx, int64_t n, int64_t C,
+                          const int64_t* label, int64_t* correct, int64_t* seen, void* stream);
+
+/* The end of a regression epoch over the collected pred / y (fp32, contiguous,
+ * N = min(*count, capacity) values each, *count int64 in device memory: the
+ * collector's cursor): ZINC's summed |out - y|
+ * (main_zinc_HL_HGCNN_dense_int3_pyr.py:165-177) and the notebook's L1, RMSE
+ * and standardised correlation (OHBM_DEMO.ipynb, train / test cells).  In
+ * fp64, two passes, one workgroup, a fixed tree:
+ *   out[0..7] = N, sum |d|, sum d^2 (d = pred - y), mean_p, mean_y,
+ *               std_p, std_y (unbiased, torch's .std()),
+ *               corr = sum (p - mean_p)(y - mean_y) / (N std_p std_y)
+ *                    = mean(z(pred) * z(y)).
+ * N == 0: the means are NaN; N < 2 or a zero deviation: corr is NaN, as in
+ * torch. */
+int hlhgat_regression_summary(const float* pred, const float* y, const int64_t* count,
+                              int64_t capacity, double* out, void* stream);
+
 /* ---- workspaces --------------------------------------------------------- */
 /* Zero `bytes` (a multiple of 4) at p with a kernel on `stream` (graph-capture
  * safe; used to initialise the BatchNorm workspace counters). */
@@ -990,8 +1049,11 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
  * index; its row was left out of the loss and the gradient */
 #define HLHGAT_DEVERR_LABEL 4u
 /* hlhgat_average_precision: a label that is neither NaN, 0 nor 1; its row was
- * counted as a negative */
+ * counted as a negative.  hlhgat_f1_per_graph: a label other than 0 or 1,
+ * counted as a negative.  hlhgat_argmax_correct: a label outside [0, C) */
 #define HLHGAT_DEVERR_METRIC_LABEL 8u
+/* hlhgat_collect_rows: the rows did not fit the buffer; none was appended */
+#define HLHGAT_DEVERR_METER_FULL 16u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 
