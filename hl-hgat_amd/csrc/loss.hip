@@ -1,7 +1,9 @@
 // Training objectives of the reference's main_*.py loops that reduce to one
 // scalar: BCE-with-logits over an on-device selection (mean / sum / the focal
 // form of lib/Loss_function.py:14-26) and row-wise cross-entropy
-// (torch.nn.CrossEntropyLoss, main_cifar10SP...:137,203).
+// (torch.nn.CrossEntropyLoss, main_cifar10SP...:137,203); and, in the simpler
+// one-workgroup form of the L1 / BCE entries of runtime.hip, the brain
+// notebook's mean squared error (section (c) below).
 //
 // Reduction structure (both families).  No floating-point atomics and no
 // hand-off between workgroups inside a launch.  The forward is a grid kernel
@@ -332,6 +334,46 @@ __global__ __launch_bounds__(kThreads) void k_cross_entropy_bwd(CeArgs p,
 
 bool gamma_ok(float g) { return g == 0.f || g >= 1.f; }  // false for NaN
 
+// --- (c) mean squared error (torch.nn.MSELoss) ---------------------------------
+// The regression loss of the brain notebook (OHBM_DEMO.ipynb: criterion =
+// torch.nn.MSELoss(); its test() accumulates the same sum as `rmse +=`).  The
+// conventions of the L1 and BCE-with-logits entries (runtime.hip): one launch
+// each way, a device scalar upstream gradient, nothing returns to the host.
+//   forward  loss = (sum_i (x_i - y_i)^2) / div  (div = n: "mean", 1: "sum");
+//            one workgroup, thread t sums elements t, t + 256, ... in order,
+//            then one LDS tree.
+//   backward dx_i = (x_i - y_i) * (2 g / div).
+// A NaN in x or y reaches the loss and its own dx element, as in torch.
+__global__ __launch_bounds__(kThreads) void k_mse_loss_fwd(const float* __restrict__ x,
+                                                           const float* __restrict__ y,
+                                                           int64_t n, float div,
+                                                           float* __restrict__ loss) {
+  __shared__ float red[kThreads];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += kThreads) {
+    const float d = x[i] - y[i];
+    s += d * d;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = red[0] / div;
+}
+
+__global__ __launch_bounds__(kThreads) void k_mse_loss_bwd(const float* __restrict__ x,
+                                                           const float* __restrict__ y,
+                                                           int64_t n, float div,
+                                                           const float* __restrict__ gout,
+                                                           float* __restrict__ dx) {
+  const float q = (2.f * gout[0]) / div;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kThreads)
+    dx[i] = (x[i] - y[i]) * q;
+}
+
 }  // namespace
 }  // namespace hlhgat
 
@@ -467,6 +509,28 @@ extern "C" int hlhgat_cross_entropy_bwd(const float* x, int64_t ldx, int64_t row
   if (grid > 2048) grid = 2048;
   launch(k_cross_entropy_bwd, dim3((unsigned)grid), dim3(kThreads), 0, as_stream(stream), nullptr,
          p, stats, gout, dx, lddx);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_mse_loss_fwd(const float* x, const float* y, int64_t n, float div,
+                                   float* loss, void* stream) {
+  HLH_CHECK_ARG(n > 0 && x && y && loss && div > 0.f,
+                "mse_loss_fwd: NULL pointer, n <= 0 or div <= 0");
+  launch(k_mse_loss_fwd, dim3(1), dim3(kThreads), 0, as_stream(stream), nullptr, x, y, n, div,
+         loss);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_mse_loss_bwd(const float* x, const float* y, int64_t n, float div,
+                                   const float* gout, float* dx, void* stream) {
+  HLH_CHECK_ARG(n > 0 && x && y && gout && dx && div > 0.f,
+                "mse_loss_bwd: NULL pointer, n <= 0 or div <= 0");
+  int64_t g = ceil_div(n, kThreads);
+  if (g > 1024) g = 1024;
+  launch(k_mse_loss_bwd, dim3((unsigned)g), dim3(kThreads), 0, as_stream(stream), nullptr, x, y,
+         n, div, gout, dx);
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }

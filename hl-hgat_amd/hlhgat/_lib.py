@@ -161,6 +161,8 @@ SIGNATURES = {
     "hlhgat_regression_summary": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hlhgat_bce_logits_fwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "hlhgat_bce_logits_bwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "hlhgat_mse_loss_fwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
+    "hlhgat_mse_loss_bwd": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_l1_loss_fwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hlhgat_l1_loss_bwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "hlhgat_loss_workspace_bytes": (c_sz, [c_i64]),

@@ -524,7 +524,7 @@ def static_caps(b: "Batch", quantum: int = 512) -> Dict[str, int]:
     return caps
 
 
-def pool_tables(datas: Sequence["Batch"]) -> None:
+def pool_tables(datas: Sequence["Batch"], pos: bool = False) -> None:
     """The attpool heads' MLGC cluster CSR per side, built on the host once
     per level list instead of inside every step (lib/Hodge_ST_Model.py:
     1029-1038, 1067-1069): fine row r of datas[0] belongs to coarse cluster
@@ -533,27 +533,36 @@ def pool_tables(datas: Sequence["Batch"]) -> None:
     the mean leaves out.  datas[0].pool_rowptr_{t,s} (int32 [n_coarse + 2])
     and pool_rows_{t,s} (int32 [n_fine], the fine rows grouped by cluster,
     ascending within one) are the CSR hodge_cheb_conv.cluster_mean sorts on
-    the device -- the same members in the same order."""
-    d0, d1 = datas[0], datas[1]
-    for side, cnt in (("t", "num_node1"), ("s", "num_edge1")):
-        x0 = np.asarray(getattr(d0, "x_" + side)[:, 0], dtype=np.float32)
-        n = x0.size
-        n_seg = int(getattr(d1, "x_" + side).shape[0])
-        counts = np.asarray(getattr(d0, cnt), dtype=np.int64)
-        ahead = np.zeros(counts.size, dtype=np.float32)
-        ahead[1:] = np.cumsum(np.asarray(getattr(d1, cnt), dtype=np.int64))[:-1]
-        per_row = np.zeros(n, dtype=np.float32)
-        k = min(int(counts.sum()), n)
-        per_row[:k] = np.repeat(ahead, counts)[:k]
-        pos = x0 + per_row  # float32, as the device forward adds them
-        idx = np.where(np.isinf(pos), n_seg, pos).astype(np.int64)
-        if idx.size and (idx.min() < 0 or idx.max() > n_seg):
-            raise ValueError(f"pool_tables: cluster ids outside [0, {n_seg}] on side {side}")
-        order = np.argsort(idx, kind="stable")
-        rowptr = np.zeros(n_seg + 2, dtype=np.int32)
-        rowptr[1:] = np.cumsum(np.bincount(idx, minlength=n_seg + 1)).astype(np.int32)
-        setattr(d0, "pool_rowptr_" + side, torch.from_numpy(rowptr))
-        setattr(d0, "pool_rows_" + side, torch.from_numpy(order.astype(np.int32)))
+    the device -- the same members in the same order.
+
+    pos=True: the brain model's level lists (HL-HGAT-DEMO/lib/
+    Hodge_Cheb_Conv.py:334-343), whose level p carries the cluster of every
+    node / edge in pos_t / pos_s (inf = dropped) instead of feature column 0;
+    every level but the last gets the tables towards the next one."""
+    pairs = list(zip(datas[:-1], datas[1:])) if pos else [(datas[0], datas[1])]
+    for d0, d1 in pairs:
+        for side, cnt in (("t", "num_node1"), ("s", "num_edge1")):
+            if pos:
+                x0 = np.asarray(getattr(d0, "pos_" + side), dtype=np.float32).reshape(-1)
+            else:
+                x0 = np.asarray(getattr(d0, "x_" + side)[:, 0], dtype=np.float32)
+            n = x0.size
+            n_seg = int(getattr(d1, "x_" + side).shape[0])
+            counts = np.asarray(getattr(d0, cnt), dtype=np.int64).reshape(-1)
+            ahead = np.zeros(counts.size, dtype=np.float32)
+            ahead[1:] = np.cumsum(np.asarray(getattr(d1, cnt), dtype=np.int64).reshape(-1))[:-1]
+            per_row = np.zeros(n, dtype=np.float32)
+            k = min(int(counts.sum()), n)
+            per_row[:k] = np.repeat(ahead, counts)[:k]
+            cl = x0 + per_row  # float32, as the device forward adds them
+            idx = np.where(np.isinf(cl), n_seg, cl).astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() > n_seg):
+                raise ValueError(f"pool_tables: cluster ids outside [0, {n_seg}] on side {side}")
+            order = np.argsort(idx, kind="stable")
+            rowptr = np.zeros(n_seg + 2, dtype=np.int32)
+            rowptr[1:] = np.cumsum(np.bincount(idx, minlength=n_seg + 1)).astype(np.int32)
+            setattr(d0, "pool_rowptr_" + side, torch.from_numpy(rowptr))
+            setattr(d0, "pool_rows_" + side, torch.from_numpy(order.astype(np.int32)))
 
 
 def level_caps(levels: Sequence[Sequence["Batch"]], quantum: int = 512) -> List[Dict[str, int]]:

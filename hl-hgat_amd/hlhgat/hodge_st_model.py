@@ -808,12 +808,32 @@ def _demo_block(cin_t, cin_s, cout, K, dropout_ratio, leaky_slope=0.1):
     return Sequential("x_t, adj_t, x_s, adj_s", layers)
 
 
-def _uniform_count(counts, what: str) -> int:
+def _uniform_count(counts, what: str, rows: int = None) -> int:
+    """The common per-graph count.  Host counts are checked value by value;
+    counts on a device are never read back (a host sync, and an error inside a
+    hipGraph capture): the count is then what ``rows`` rows over that many
+    graphs imply, and only divisibility can be checked."""
+    if torch.is_tensor(counts) and counts.is_cuda and rows is not None:
+        n_graphs = counts.numel()
+        if n_graphs == 0 or rows % n_graphs != 0:
+            raise ValueError(f"HL_HGAT_attpool: every graph of a batch must have the same number "
+                             f"of {what} (the head flattens them per graph); got {rows} rows "
+                             f"for {n_graphs} graphs")
+        return rows // n_graphs
     c = torch.as_tensor(counts).view(-1).tolist()
     if len(set(int(v) for v in c)) != 1:
         raise ValueError(f"HL_HGAT_attpool: every graph of a batch must have the same number of "
                          f"{what} (the head flattens them per graph); got {sorted(set(c))}")
     return int(c[0])
+
+
+def _brain_degree(data, n: int, dev) -> torch.Tensor:
+    """_node_degree for the brain head's levels, which may be plain objects on
+    another device than the model's (the forward moves what it reads)."""
+    d = getattr(data, "deg_t", None)
+    if torch.is_tensor(d) and d.device == dev and d.numel() == n:
+        return d
+    return degree(data.edge_index.to(dev).view(-1), num_nodes=n)
 
 
 class HL_HGAT_attpool(nn.Module):
@@ -891,12 +911,17 @@ class HL_HGAT_attpool(nn.Module):
         data = datas[0]
         n_graphs = int(torch.as_tensor(data.num_node1).numel())
         for p, d in enumerate(datas):
-            _uniform_count(d.num_node1, f"nodes (level {p})")
-            _uniform_count(d.num_edge1, f"edges (level {p})")
-        # global coarse index of every node / edge of level p (:334-343)
+            _uniform_count(d.num_node1, f"nodes (level {p})", d.x_t.size(0))
+            _uniform_count(d.num_edge1, f"edges (level {p})", d.x_s.size(0))
+        # global coarse index of every node / edge of level p (:334-343); not
+        # needed (None) when level p carries its cluster CSR (pool_tables)
         pos_ts, pos_ss = [], []
         for p in range(n_pool):
             d, dn = datas[p], datas[p + 1]
+            if _has_pool_tables(d, dev):
+                pos_ts.append(None)
+                pos_ss.append(None)
+                continue
             pos_ts.append(d.pos_t.to(dev).view(-1).to(torch.float32) + _level_offsets(
                 dn.num_node1, d.num_node1, dev, d.x_t.size(0)))
             pos_ss.append(d.pos_s.to(dev).view(-1).to(torch.float32) + _level_offsets(
@@ -909,7 +934,7 @@ class HL_HGAT_attpool(nn.Module):
         x_t0, x_s0 = x_t, x_s
         k = 0
         par_1 = adj2par1(data.edge_index.to(dev), x_t0.shape[0], x_s0.shape[0])
-        D = degree(data.edge_index.to(dev).view(-1), num_nodes=x_t0.shape[0]) + 1e-6
+        D = _brain_degree(data, x_t0.shape[0], dev) + 1e-6
         node_att = edge_att = None
         for i, _ in enumerate(self.channels):
             for j in range(self.channels[i]):
@@ -924,13 +949,13 @@ class HL_HGAT_attpool(nn.Module):
                 x_t0 = ops.row_scale(x_t0, att_t)
                 x_s0 = ops.row_scale(x_s0, att_s)
                 dn = datas[k + 1]
-                x_t0 = cluster_mean(x_t0, pos_ts[k], dn.x_t.shape[0])
-                x_s0 = cluster_mean(x_s0, pos_ss[k], dn.x_s.shape[0])  # inf members dropped
+                x_t0 = _pool(x_t0, pos_ts[k], datas[k], "t", dn.x_t.shape[0])
+                x_s0 = _pool(x_s0, pos_ss[k], datas[k], "s", dn.x_s.shape[0])  # inf dropped
                 adj_t = (dn.edge_index_t.to(dev), dn.edge_weight_t.to(dev))
                 adj_s = (dn.edge_index_s.to(dev), dn.edge_weight_s.to(dev))
                 k += 1
                 par_1 = adj2par1(dn.edge_index.to(dev), x_t0.shape[0], x_s0.shape[0])
-                D = degree(dn.edge_index.to(dev).view(-1), num_nodes=x_t0.shape[0]) + 1e-6
+                D = _brain_degree(dn, x_t0.shape[0], dev) + 1e-6
         x_t, x_s = self.readout(x_t, adj_t, x_s, adj_s)
         x = torch.cat([x_s.view(n_graphs, -1), x_t.view(n_graphs, -1)], dim=-1)
         if x.size(1) != self.num_nodepedge:

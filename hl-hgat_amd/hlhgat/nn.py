@@ -16,8 +16,9 @@ from typing import Callable, List, Sequence, Tuple, Union
 import torch
 import torch.nn as tnn
 
-__all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "BCEWithLogitsLoss", "FocalLoss",
-           "MaskedBCEWithLogitsLoss", "CrossEntropyLoss", "glorot", "global_mean_pool"]
+__all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "MSELoss", "BCEWithLogitsLoss",
+           "FocalLoss", "MaskedBCEWithLogitsLoss", "CrossEntropyLoss", "glorot",
+           "global_mean_pool"]
 
 
 def glorot(t: torch.Tensor) -> None:
@@ -144,6 +145,26 @@ class BCEWithLogitsLoss(tnn.BCEWithLogitsLoss):
                 and not target.requires_grad and 0 < input.numel() <= self.FUSED_MAX):
             from . import ops
             return ops.bce_with_logits(input, target, self.reduction)
+        return super().forward(input, target)
+
+
+class MSELoss(tnn.MSELoss):
+    """torch.nn.MSELoss (the brain notebook's training criterion,
+    OHBM_DEMO.ipynb) whose "mean" / "sum" reductions on ROCm fp32 tensors run
+    as one HIP launch each way (ops.mse_loss) up to BCEWithLogitsLoss.FUSED_MAX
+    elements, for that class's reason: the forward is one workgroup.  CPU
+    tensors, "none", a target that needs a gradient, unequal (broadcast)
+    shapes and larger inputs go to torch."""
+
+    FUSED_MAX = BCEWithLogitsLoss.FUSED_MAX
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if (self.reduction in ("mean", "sum") and input.is_cuda and target.is_cuda
+                and input.dtype == torch.float32 and target.dtype == torch.float32
+                and input.shape == target.shape and not target.requires_grad
+                and 0 < input.numel() <= self.FUSED_MAX):
+            from . import ops
+            return ops.mse_loss(input, target, self.reduction)
         return super().forward(input, target)
 
 

@@ -32,7 +32,7 @@ __all__ = [
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
-    "bce_logits_loss", "cross_entropy", "average_precision",
+    "bce_logits_loss", "cross_entropy", "mse_loss", "average_precision",
     "collect_rows", "f1_per_graph", "argmax_correct", "regression_summary",
     "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
@@ -2372,6 +2372,45 @@ def bce_with_logits(input: torch.Tensor, target: torch.Tensor,
         raise ValueError(f"hlhgat: bce_with_logits reduction {reduction!r}")
     div = float(input.numel()) if reduction == "mean" else 1.0
     return _BCELogitsFn.apply(input.contiguous(), target.to(torch.float32).contiguous(), div)
+
+
+class _MSELossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, div):
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        check(LIB.hlhgat_mse_loss_fwd(x.data_ptr(), y.data_ptr(), x.numel(), div,
+                                      loss.data_ptr(), _stream(x)), "mse_loss_fwd")
+        ctx.div = div
+        ctx.save_for_backward(x, y)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        check(LIB.hlhgat_mse_loss_bwd(x.data_ptr(), y.data_ptr(), x.numel(), ctx.div,
+                                      g.data_ptr(), dx.data_ptr(), _stream(x)), "mse_loss_bwd")
+        return dx, None, None
+
+
+def mse_loss(input: torch.Tensor, target: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    """F.mse_loss(input, target, reduction=...) for "mean" / "sum", one launch
+    each way (hlhgat_mse_loss_fwd / _bwd): the brain notebook's training
+    criterion.  The loss value is the fp32 sum of squares in a fixed order;
+    dx = (x - y) * (2 g / div).  No gradient flows into target."""
+    _req_dev(input, "input")
+    if input.shape != target.shape:
+        raise RuntimeError(f"hlhgat: mse_loss shapes differ: {tuple(input.shape)} vs "
+                           f"{tuple(target.shape)}")
+    if target.requires_grad:
+        raise RuntimeError("hlhgat: mse_loss: target must not require grad")
+    if input.numel() == 0:
+        raise RuntimeError("hlhgat: mse_loss of an empty tensor")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"hlhgat: mse_loss reduction {reduction!r}")
+    div = float(input.numel()) if reduction == "mean" else 1.0
+    return _MSELossFn.apply(input.contiguous(), target.to(torch.float32).contiguous(), div)
 
 
 def _loss_workspace(n: int, like: torch.Tensor) -> Optional[torch.Tensor]:

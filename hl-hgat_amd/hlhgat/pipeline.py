@@ -52,7 +52,8 @@ import numpy as np
 import torch
 
 from .hodge_dataset import (Batch, PairData, _h2d, collate, dense_to_sparse, graclus,
-                            hodge_laplacians, mlgc_batch, mlgc_batch_flat, mlgc_map)
+                            hodge_laplacians, mlgc_batch, mlgc_batch_flat, mlgc_map,
+                            pool_tables)
 
 __all__ = ["SuperpixelPipeline", "to_undirected_min", "superpixel_raw", "BrainPipeline",
            "brain_target"]
@@ -514,8 +515,15 @@ class BrainPipeline:
                     g.x_t = torch.zeros(self.N, 1)
                     g.x_s = torch.zeros(self.E, 1)
                     g.y = None
-                b = collate([g] * int(B), check_hodge=True)
-                out.append(b.to(dev) if dev.type == "cuda" else b)
+                out.append(collate([g] * int(B), check_hodge=True))
+            # the cluster CSR of every pooled level next to the CSR, incidence
+            # and degree tables of collate: the head then sorts no cluster
+            # assignment in its forward (HL_HGAT_attpool, hodge_st_model._pool)
+            if len(out) > 1 and all(torch.is_tensor(getattr(b, k, None))
+                                    for b in out[:-1] for k in ("pos_t", "pos_s")):
+                pool_tables(out, pos=True)
+            if dev.type == "cuda":
+                out = [b.to(dev) for b in out]
             self._levels[key] = out
         return out
 

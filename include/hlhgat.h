@@ -850,6 +850,23 @@ int hlhgat_bce_logits_fwd(const float* x, const float* y, int64_t n, float div, 
 int hlhgat_bce_logits_bwd(const float* x, const float* y, int64_t n, float div,
                           const float* gout, float* dx, void* stream);
 
+/* Mean squared error (csrc/loss.hip), torch.nn.MSELoss of the brain notebook
+ * (HL-HGAT-DEMO/OHBM_DEMO.ipynb: `criterion = torch.nn.MSELoss()` in the
+ * training cell; its test() accumulates the same sum of squares in the
+ * `rmse += ...` line).  The conventions of the two entries above:
+ *   fwd: loss[0] = (sum_i (x_i - y_i)^2) / div  (div = n: "mean", 1: "sum");
+ *        one launch, one workgroup: thread t adds elements t, t + 256, ... in
+ *        order, then one LDS tree.  No floating-point atomics, no host read;
+ *   bwd: dx_i = (x_i - y_i) * (2 gout[0] / div), one grid-stride launch, gout
+ *        a device scalar.
+ * A NaN in x or y gives a NaN loss and a NaN in its own dx element only, as
+ * in torch.  n > 0, div > 0 and non-NULL pointers, checked before any launch
+ * (HLHGAT_ERR_ARG). */
+int hlhgat_mse_loss_fwd(const float* x, const float* y, int64_t n, float div, float* loss,
+                        void* stream);
+int hlhgat_mse_loss_bwd(const float* x, const float* y, int64_t n, float div, const float* gout,
+                        float* dx, void* stream);
+
 /* ---- reduced training losses (csrc/loss.hip) ----------------------------- */
 /* Structure shared by the two families below.  No floating-point atomics and
  * no hand-off between workgroups inside a launch: the forward is a grid kernel

@@ -20,11 +20,20 @@
     torch's conv1d / max_pool1d (MIOpen), for the ratio -- or the note that it
     did not finish.
 
+(e) --train-step, a run of its own (profiles/brain_train_step.json): the
+    notebook's training step -- HL_HGAT_attpool at the checkpoint shape on 5
+    copies of the skeleton, T = 375, hlhgat.nn.MSELoss, Adam(lr=1e-4,
+    weight_decay=1e-4) -- under TrainStep(graphs=False) and
+    TrainStep(graphs=True) in the same process: events and wall time per step
+    (median of 20 after 5 warm-up steps), and the replayed step's copy of the
+    batch into the graph's static buffers (_Captured.load) on its own.
+
 Event timing after warm-up, median of --reps runs.
 """
 from __future__ import annotations
 
 import argparse
+import copy
 import json
 import os
 import subprocess
@@ -301,6 +310,82 @@ def input_pipeline(reps):
     return res
 
 
+def timed_wall(fn, reps, warmup):
+    """(event ms, wall ms) per call, medians; the wall time includes the wait
+    for the device to finish the call's work."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev, wall = [], []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ev.append(a.elapsed_time(b))
+    return round(float(np.median(ev)), 4), round(float(np.median(wall)), 4)
+
+
+def train_step(reps=20, warmup=5):
+    """(e) the notebook's training step, eager against replayed."""
+    import hlhgat
+    from hlhgat import ops
+    from hlhgat.train import TrainStep, batch_key
+    dev = torch.device("cuda:0")
+    B, S = 5, 10
+    fine, coarse, c_node, c_edge = skeleton_levels()
+    fine.pos_t, fine.pos_s = c_node.view(-1), c_edge.view(-1)
+    n, E = int(fine.num_node1), int(fine.num_edge1)
+    n1, E1 = int(coarse.num_node1), int(coarse.num_edge1)
+    rng = np.random.default_rng(0)
+    series = [((rng.standard_normal((n, 6)) @ rng.standard_normal((6, T))
+                + rng.standard_normal((n, T))) * 50 + 1000).astype(np.float32) for _ in range(S)]
+    targets = rng.standard_normal(S).astype(np.float32)
+    pipe = hlhgat.BrainPipeline(series, targets, [fine, coarse])
+    batches = [pipe.batch([(k * B + j) % S for j in range(B)], device=dev) for k in range(2)]
+    batches = [[copy.copy(b[0])] + b[1:] for b in batches]
+    for b in batches:  # the pipeline reuses its workspace: keep each batch's own values
+        b[0].x_t, b[0].x_s = b[0].x_t.clone(), b[0].x_s.clone()
+    mse = hlhgat.nn.MSELoss()
+    res = {"graphs": B, "nodes": n, "edges": E, "coarse_nodes": n1, "coarse_edges": E1, "T": T,
+           "reps": reps, "warmup": warmup, "parent_eager_head_fwd_bwd_ms": 9.87}
+    first = {}
+    for graphs in (False, True):
+        torch.manual_seed(0)
+        m = hlhgat.HL_HGAT_attpool(channels=[2, 2, 2], filters=[32, 64, 128], mlp_channels=[],
+                                   K=4, pool_num=1, num_nodepedge=n1 + E1).to(dev).train()
+        step = TrainStep(m, lambda o, d: mse(o[0], d[0].y.view(-1, 1)), lr=1e-4,
+                         weight_decay=1e-4, graphs=graphs)
+        first[graphs] = float(step(batches[0]))
+        it = [0]
+
+        def one():
+            it[0] += 1
+            return step(batches[it[0] % len(batches)])
+
+        ev, wall = timed_wall(one, reps, warmup)
+        name = "replayed" if graphs else "eager"
+        res[name] = {"step_event_ms": ev, "step_wall_ms": wall, "stats": dict(step.stats)}
+        ops.check_device_errors()
+        if graphs:
+            ent = step._graphs[batch_key(batches[0])]
+            lev, lwall = timed_wall(lambda: ent.load(batches[(it[0] + 1) % len(batches)]), reps,
+                                    warmup)
+            tensors = [v for b in batches[0] for k, v in vars(b).items()
+                       if torch.is_tensor(v) and not k.startswith("_")]
+            res["load"] = {"event_ms": lev, "wall_ms": lwall, "tensors": len(tensors),
+                           "mbytes": round(sum(v.numel() * v.element_size()
+                                               for v in tensors) / 1e6, 3),
+                           "share_of_replayed_step_event": round(lev / ev, 4)}
+    res["first_loss_equal"] = first[False] == first[True]
+    res["ratio_eager_over_replayed_event"] = round(
+        res["eager"]["step_event_ms"] / res["replayed"]["step_event_ms"], 3)
+    return res
+
+
 def torch_child(args, res):
     """Last GPU step of the run: torch's own ops in a child with a time limit."""
     t0 = time.time()
@@ -333,7 +418,19 @@ def main():
                     help="the input-pipeline leg alone, merged into an existing --out file")
     ap.add_argument("--skip-torch", action="store_true",
                     help="no torch-ops child (e.g. under a kernel trace)")
+    ap.add_argument("--train-step", action="store_true",
+                    help="the training-step leg alone (eager against replayed), written to "
+                         "--train-out")
+    ap.add_argument("--train-out", default=os.path.join(REPO, "profiles",
+                                                        "brain_train_step.json"))
     args = ap.parse_args()
+    if args.train_step:
+        res = train_step()
+        os.makedirs(os.path.dirname(args.train_out), exist_ok=True)
+        with open(args.train_out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if args.torch_only:
         print(json.dumps(front_end(TorchInception1D(), args.reps)), flush=True)
         return
