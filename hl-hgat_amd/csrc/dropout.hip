@@ -21,33 +21,10 @@
 // pointers and leading dimensions), a scalar path otherwise.  No atomics;
 // plain vector stores only.
 #include "common.h"
+#include "philox.h"
 
 namespace hlhgat {
 namespace {
-
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-
-struct Philox4 {
-  uint32_t w[4];
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2,
-                                                 uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
-    const uint32_t hi1 = __umulhi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0;
-    c1 = lo1;
-    c2 = n2;
-    c3 = lo0;
-    k0 += kPhiloxW0;
-    k1 += kPhiloxW1;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
 
 struct DropArgs {
   const float* src;  // fwd: x; bwd: dy

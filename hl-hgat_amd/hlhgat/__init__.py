@@ -24,6 +24,7 @@ from . import metrics  # noqa: F401,E402
 from .metrics import (AccuracyMeter, Collector, F1Meter, RegressionMeter,  # noqa: F401,E402
                       eval_ap)
 from .nn import (BatchNorm, CrossEntropyLoss, FocalLoss, Linear,  # noqa: F401,E402
-                 MaskedBCEWithLogitsLoss, MSELoss, Sequential, global_mean_pool)
+                 MaskedBCEWithLogitsLoss, MSELoss, Sequential, SimplexDropout,
+                 global_mean_pool)
 
 __version__ = "0.1.0"

@@ -130,7 +130,11 @@ SIGNATURES = {
     "hlhgat_dropout_bwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, C.c_uint32, c_f32, c_vp,
                                    C.c_uint32, c_vp, c_i64, c_vp]),
     "hlhgat_dropout_advance": (c_i32, [c_vp, c_vp]),
-    "hlhgat_edge_absdiff": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+    "hlhgat_simplex_keep": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_uint32, C.c_uint32,
+                                    C.c_uint32, C.c_uint32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "hlhgat_mask_csr_values": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "hlhgat_mask_hodge_factor": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hlhgat_edge_absdiff":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                                     c_vp]),
     "hlhgat_pool_mean_bwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                                      c_i64, c_vp]),

@@ -388,8 +388,17 @@ class HL_HGCNN_TSP_dense_int3_pyr(nn.Module):
             (HodgeLaguerreConv(mlp_insize, num_classes, K=1),
              "x_t, edge_index_t, edge_weight_t -> x_t")])
         self.readout_abs = Abs()  # |B1^T x_t| (:848); a module so the gates can freeze its signs
+        # the training set's structural augmentation (TSP_EigPE.get with
+        # if_aug=True, main_TSP_HL_HGCNN_dense_int3_pyr.py:119-139, :404) as a
+        # submodule: an nn.SimplexDropout, or None (the shipped scripts'
+        # behaviour, which never reach dropout_node's body); no state_dict keys
+        self.register_module("augment", None)
 
     def forward(self, data, device="cuda:0"):
+        if self.augment is not None:
+            # training: draws the keep mask into x_s[:, 1] and masks L1 in
+            # place; eval: no launch, the unmasked operator
+            self.augment(data)
         dev = data.x_s.device
         # output_size given: no host sync (the step can be captured)
         s_batch = _per_row(torch.arange(data.num_edge1.numel(), device=dev), data.num_edge1,

@@ -18,7 +18,7 @@ import torch.nn as tnn
 
 __all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "MSELoss", "BCEWithLogitsLoss",
            "FocalLoss", "MaskedBCEWithLogitsLoss", "CrossEntropyLoss", "glorot",
-           "global_mean_pool"]
+           "global_mean_pool", "SimplexDropout"]
 
 
 def glorot(t: torch.Tensor) -> None:
@@ -556,3 +556,96 @@ def global_mean_pool(x: torch.Tensor, batch: torch.Tensor, size: int = None) -> 
     ptr = torch.zeros(size + 1, dtype=torch.int32, device=x.device)
     ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
     return segment_mean(x, ptr, size)
+
+
+class SimplexDropout(tnn.Module):
+    """The structural augmentation of the TSP training set, on the device and
+    under graph replay: TSP_EigPE.get with if_aug=True
+    (main_TSP_HL_HGCNN_dense_int3_pyr.py:119-139 == lib/Hodge_Dataset.py:
+    690-708) sends a share ``aug_prob`` of the samples through dropout_node
+    (:73-97), which drops every simplex whose uniform draw is not above the
+    sample's rate ``p + U * jitter`` (the reference: p + U / 2) unless it is on
+    the tour (y_loc), filters the Laplacian's COO to the surviving simplices
+    without relabelling, and appends the keep mask as a column of x.
+
+    Here the operator keeps its shape: ``forward(batch)`` draws the mask of
+    every graph of the batch (ops.simplex_keep: counter-based, on the dropout
+    state shared with the feature Dropout, so TrainStep's one advance per step
+    serves both and a captured step draws fresh masks on every replay), writes
+    it into column ``mask_column`` of ``x_<side>`` in place, binds it to
+    ``edge_index_<side>`` (ops.set_row_mask) and rewrites the masked operator
+    tables (ops.refresh_row_mask): at most 3 launches, 4 with halo tiles.
+    ``protect`` names the batch attribute whose non-zero rows are never dropped
+    (None: none).  ``site`` is the module's ordinal k: modules with different
+    k draw independent masks.  In eval mode nothing is launched and a mask this
+    module bound earlier is unbound, so the unmasked operator runs.  Leaving
+    the module off reproduces the shipped training scripts, which never pass
+    p.  No parameters, no buffers; CPU tensors raise (no CPU path)."""
+
+    def __init__(self, aug_prob: float = 0.75, p: float = 0.0, jitter: float = 0.5,
+                 side: str = "s", protect: Union[str, None] = "y", mask_column: Union[int, None] = 1,
+                 site: int = 0):
+        super().__init__()
+        from .ops import simplex_thresholds
+        simplex_thresholds(aug_prob, p, jitter)  # range checks
+        if side not in ("s", "t"):
+            raise ValueError(f"SimplexDropout: side must be 's' or 't' (got {side!r})")
+        if not 0 <= int(site) < (1 << 30):
+            raise ValueError(f"SimplexDropout: site {site} out of range")
+        self.aug_prob, self.p, self.jitter = float(aug_prob), float(p), float(jitter)
+        self.side, self.protect, self.mask_column, self.site = side, protect, mask_column, int(site)
+
+    def extra_repr(self) -> str:
+        return (f"aug_prob={self.aug_prob}, p={self.p}, jitter={self.jitter}, side={self.side!r}, "
+                f"protect={self.protect!r}, mask_column={self.mask_column}, site={self.site}")
+
+    def mask_of(self, batch) -> Union[torch.Tensor, None]:
+        """The mask tensor this module draws into for ``batch`` (None before
+        the first training forward on it)."""
+        ei = getattr(batch, "edge_index_" + self.side)
+        return getattr(ei, "_hlhgat_simplex_masks", {}).get(self.site)
+
+    def forward(self, batch):
+        from . import ops
+        s = self.side
+        x, ei, w = (getattr(batch, k + s, None) for k in ("x_", "edge_index_", "edge_weight_"))
+        if not (torch.is_tensor(x) and torch.is_tensor(ei) and torch.is_tensor(w)):
+            raise RuntimeError(f"SimplexDropout: the batch needs x_{s}, edge_index_{s} and "
+                               f"edge_weight_{s}")
+        own = getattr(ei, "_hlhgat_simplex_masks", {}).get(self.site)
+        if not self.training:
+            bound = getattr(ei, "_hlhgat_row_mask", None)
+            if own is not None and bound is not None and bound[0] is own:
+                ops.set_row_mask(ei, None)
+            return batch
+        if not (x.is_cuda and ei.is_cuda and w.is_cuda):
+            raise RuntimeError("SimplexDropout: the batch must be on a ROCm device (got "
+                               f"{x.device}); the HIP path has no CPU fallback")
+        seg = getattr(batch, "seg_ptr_" + s, None)
+        if not torch.is_tensor(seg):
+            raise RuntimeError(f"SimplexDropout: the batch has no seg_ptr_{s} (hodge_dataset."
+                               f"collate builds it from the per-graph row counts)")
+        n = x.size(0)
+        col = None
+        if self.mask_column is not None:
+            if x.dim() != 2 or not 0 <= self.mask_column < x.size(1):
+                raise RuntimeError(f"SimplexDropout: x_{s} {tuple(x.shape)} has no column "
+                                   f"{self.mask_column}")
+            col = x[:, self.mask_column]
+        prot = None
+        if self.protect is not None:
+            prot = getattr(batch, self.protect, None)
+            if not torch.is_tensor(prot) or prot.numel() != n:
+                raise RuntimeError(f"SimplexDropout: batch.{self.protect} must hold one entry per "
+                                   f"row of x_{s} ({n})")
+            prot = prot.view(n)
+        if own is None or own.numel() != n or own.device != x.device:
+            if not hasattr(ei, "_hlhgat_simplex_masks"):
+                ei._hlhgat_simplex_masks = {}
+            own = ei._hlhgat_simplex_masks[self.site] = torch.empty(n, device=x.device,
+                                                                   dtype=torch.float32)
+        ops.simplex_keep(seg, own, self.aug_prob, self.p, self.jitter, self.site, protect=prot,
+                         column=col)
+        ops.set_row_mask(ei, own)
+        ops.refresh_row_mask(ei, w, n)
+        return batch

@@ -28,7 +28,8 @@ except ImportError as e:  # pragma: no cover - the build always produces it
 
 __all__ = [
     "SparseCSR", "HodgeOperator", "Incidence", "hodge_operator", "incidence",
-    "mark_hodge", "spmm", "poly_basis", "hodge_poly_conv", "linear_blocks", "mlp2", "nei_value",
+    "mark_hodge", "set_row_mask", "refresh_row_mask", "simplex_keep",
+    "spmm", "poly_basis", "hodge_poly_conv", "linear_blocks", "mlp2", "nei_value",
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
@@ -313,6 +314,10 @@ class HodgeOperator:
     bwd: SparseCSR
     factor: Optional[tuple] = None
     factor_nodes: int = 0
+    # a row-masked view (set_row_mask): (the unmasked operator, the mask, the
+    # halo tiles' entry permutation or None); val / sval / the factor's sign
+    # and alpha tables are then the masked buffers
+    masked_from: Optional[tuple] = None
 
 
 @dataclass
@@ -744,7 +749,17 @@ def hodge_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor]
 
     propagate (source_to_target, aggr='add', message = norm*x_j,
     lib/Hodge_Cheb_Conv.py:518-519) computes Y[ei[1][e]] += w[e] * X[ei[0][e]],
-    i.e. Y = A X with A keyed by ei[1]; its adjoint is keyed by ei[0]."""
+    i.e. Y = A X with A keyed by ei[1]; its adjoint is keyed by ei[0].  With a
+    row mask bound to edge_index (set_row_mask) the operator is M A M: the
+    same rowptr / col, masked values."""
+    bound = getattr(edge_index, "_hlhgat_row_mask", None)
+    if bound is not None:
+        return _masked_operator(edge_index, edge_weight, n, bound, refresh=False)
+    return _hodge_operator(edge_index, edge_weight, n)
+
+
+def _hodge_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor],
+                    n: int) -> HodgeOperator:
     _req_dev(edge_index, "edge_index", torch.int64)
     if edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise RuntimeError(f"hlhgat: edge_index must be [2, nnz] (got {tuple(edge_index.shape)})")
@@ -785,6 +800,161 @@ def hodge_operator(edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor]
             c.valid = valid
         op = HodgeOperator(fwd, bwd)
     return _HODGE_CACHE.put(keys, n, op)
+
+
+# ----------------------------------------------------------------------------
+# Row masks on Hodge operators (simplex dropout, csrc/simplex.hip)
+# ----------------------------------------------------------------------------
+def set_row_mask(edge_index: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """Bind a row mask (fp32 [n], non-zero = kept) to a marked (sorted
+    symmetric) Laplacian's edge_index: hodge_operator then returns M L M,
+    M = diag(mask) -- the operator subgraph(node_mask, edge_index_s,
+    edge_weight_s) leaves without relabelling (dropout_node,
+    main_TSP_HL_HGCNN_dense_int3_pyr.py:93-95) on the unmasked operator's own
+    rowptr / col: its val, the factored L1's sign / alpha tables and the halo
+    tiles' sval are masked copies, allocated once per bound mask tensor.  The
+    mask is read when the operator is first built and again by every
+    refresh_row_mask (after the mask changed in place).  mask = None unbinds."""
+    if mask is None:
+        if hasattr(edge_index, "_hlhgat_row_mask"):
+            del edge_index._hlhgat_row_mask
+        return edge_index
+    if not getattr(edge_index, "_hlhgat_sorted_symmetric", False):
+        raise RuntimeError("hlhgat: set_row_mask needs a sorted symmetric Laplacian "
+                           "(mark_hodge); a general operator cannot take a row mask")
+    _req_dev(edge_index, "edge_index", torch.int64)
+    _req_dev(mask, "mask")
+    if mask.dim() != 1 or not mask.is_contiguous() or mask.device != edge_index.device:
+        raise RuntimeError(f"hlhgat: mask must be a contiguous 1-D tensor on {edge_index.device} "
+                           f"(got {tuple(mask.shape)} on {mask.device})")
+    bound = getattr(edge_index, "_hlhgat_row_mask", None)
+    if bound is None or bound[0] is not mask:
+        edge_index._hlhgat_row_mask = (mask, {})  # type: ignore[attr-defined]
+    return edge_index
+
+
+def refresh_row_mask(edge_index: torch.Tensor, edge_weight: torch.Tensor,
+                     n: int) -> HodgeOperator:
+    """Rewrite the masked tables of the operator hodge_operator(edge_index,
+    edge_weight, n) returns from the bound mask's current values: one launch
+    for the CSR values, one for the factor tables of a factored L1, one gather
+    for halo tiles; nothing is allocated after the first call.  Returns the
+    masked operator."""
+    bound = getattr(edge_index, "_hlhgat_row_mask", None)
+    if bound is None:
+        raise RuntimeError("hlhgat: refresh_row_mask: no mask bound (set_row_mask)")
+    return _masked_operator(edge_index, edge_weight, n, bound, refresh=True)
+
+
+def _masked_operator(edge_index, edge_weight, n: int, bound, refresh: bool) -> HodgeOperator:
+    mask, bufs = bound
+    if edge_weight is None:
+        raise RuntimeError("hlhgat: a row-masked operator needs edge weights")
+    if mask.numel() != n:
+        raise RuntimeError(f"hlhgat: row mask has {mask.numel()} entries, operator {n} rows")
+    keys, extra = [edge_index, edge_weight], (n, "row_mask", id(mask))
+    op = _HODGE_CACHE.get(keys, extra)
+    fresh = op is None
+    if fresh:
+        base = _hodge_operator(edge_index, edge_weight, n)
+        a = base.fwd
+
+        def buf(name, like):
+            t = bufs.get(name)
+            if t is None or t.shape != like.shape or t.device != like.device:
+                t = bufs[name] = torch.empty_like(like)
+            return t
+
+        m = SparseCSR(a.rowptr, a.col, buf("val", a.val), a.n_rows, a.n_cols, a.nnz, a.order,
+                      a.valid)
+        eperm = None
+        if a.halo is not None:
+            tp, hp, hc, srp, lcol, sval, bounds, hdr = a.halo
+            if sval is not None:
+                eperm = edge_index._hlhgat_halo[5]
+                sval = buf("sval", sval)
+            m.halo = (tp, hp, hc, srp, lcol, sval, bounds, hdr)
+        op = HodgeOperator(m, m, masked_from=(base, mask, eperm))
+        if base.factor is not None:
+            nr, ne, ns, no, ends, alpha, eo = base.factor
+            op.factor = (nr, ne, buf("sign", ns), no, ends, buf("alpha", alpha), eo)
+            op.factor_nodes = base.factor_nodes
+        _HODGE_CACHE.put(keys, extra, op)
+    if fresh or refresh:
+        base, _, eperm = op.masked_from
+        a, st = op.fwd, _stream(mask)
+        if a.n_rows and a.nnz:
+            check(LIB.hlhgat_mask_csr_values(a.rowptr.data_ptr(), a.col.data_ptr(),
+                                             base.fwd.val.data_ptr(), a.n_rows, a.nnz,
+                                             mask.data_ptr(), a.val.data_ptr(), st),
+                  "mask_csr_values")
+            if eperm is not None:
+                check(LIB.hlhgat_gather_f32(a.val.data_ptr(), eperm.data_ptr(), a.nnz,
+                                            a.halo[5].data_ptr(), st), "gather_f32")
+        if op.factor is not None and a.n_rows:
+            check(LIB.hlhgat_mask_hodge_factor(_factor_desc(base), mask.data_ptr(),
+                                               op.factor[2].data_ptr(), op.factor[5].data_ptr(),
+                                               st), "mask_hodge_factor")
+    return op
+
+
+SIMPLEX_SITE = 0x80000000  # site of SimplexDropout k: SIMPLEX_SITE + 2k (graph), + 1 (row)
+
+
+def simplex_thresholds(aug_prob: float, p: float, jitter: float) -> Tuple[int, int, int]:
+    """(Ta, Tp, Tj) = floor(. * 2^24) of the simplex-dropout rule, in double."""
+    for name, v in (("aug_prob", aug_prob), ("p", p), ("jitter", jitter)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"simplex dropout: {name} has to be between 0 and 1, but got {v}")
+    Ta, Tp, Tj = (int(math.floor(float(v) * 16777216.0)) for v in (aug_prob, p, jitter))
+    if Tp + Tj > 1 << 24:
+        raise ValueError(f"simplex dropout: p + jitter = {p} + {jitter} exceeds 1")
+    return Ta, Tp, Tj
+
+
+def simplex_keep(seg_ptr: torch.Tensor, mask: torch.Tensor, aug_prob: float, p: float,
+                 jitter: float, site: int = 0, protect: Optional[torch.Tensor] = None,
+                 column: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Draw the keep mask of dropout_node / TSP_EigPE.get
+    (main_TSP_HL_HGCNN_dense_int3_pyr.py:84-92, :125-131) for every graph of a
+    batch into ``mask`` (fp32 [n_rows], 1 = kept; rows >= seg_ptr[-1] are
+    padding and get 0) and, when given, into ``column`` (a strided [n_rows]
+    view such as x_s[:, 1]): one launch, counter-based on the shared dropout
+    state (dropout_state), so a captured launch draws a fresh mask per replay.
+    A graph is augmented with probability aug_prob; its rate is p + U * jitter;
+    rows whose ``protect`` entry (a strided fp32 [n_rows] view) is non-zero are
+    never dropped.  ``site`` is the module ordinal k."""
+    _req_dev(mask, "mask")
+    _req_dev(seg_ptr, "seg_ptr", torch.int32)
+    if mask.dim() != 1 or not mask.is_contiguous() or seg_ptr.dim() != 1 or seg_ptr.numel() < 1 \
+            or not seg_ptr.is_contiguous():
+        raise RuntimeError("hlhgat: simplex_keep: mask [n_rows] and seg_ptr [G + 1] must be "
+                           "contiguous 1-D tensors")
+    n = mask.numel()
+    for name, t in (("protect", protect), ("column", column)):
+        if t is None:
+            continue
+        _req_dev(t, name)
+        if t.dim() == 2 and t.size(1) == 1:
+            t = t[:, 0]
+        if t.dim() != 1 or t.numel() != n or (n > 1 and t.stride(0) < 1):
+            raise RuntimeError(f"hlhgat: simplex_keep: {name} must be a [n_rows] (strided) view "
+                               f"(got {tuple(t.shape)})")
+        if name == "protect":
+            protect = t
+        else:
+            column = t
+    if not 0 <= int(site) < (1 << 30):
+        raise ValueError(f"simplex dropout: site {site} out of range")
+    Ta, Tp, Tj = simplex_thresholds(aug_prob, p, jitter)
+    st = _dropout_st(mask.device)
+    ld = lambda t: max(int(t.stride(0)), 1)  # noqa: E731
+    check(LIB.hlhgat_simplex_keep(
+        seg_ptr.data_ptr(), seg_ptr.numel() - 1, n, _ptr(protect),
+        ld(protect) if protect is not None else 0, Ta, Tp, Tj, SIMPLEX_SITE + 2 * int(site),
+        st.dev.data_ptr(), mask.data_ptr(), _ptr(column), ld(column) if column is not None else 0,
+        _stream(mask)), "simplex_keep")
+    return mask
 
 
 def set_csr(edge_index: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor) -> torch.Tensor:

@@ -36,6 +36,7 @@ import torch.distributed as dist
 
 from . import ops
 from .distributed import collectives_on
+from .nn import SimplexDropout
 
 __all__ = ["Staged", "TrainStep", "InferStep", "batch_key", "forward_collectives"]
 
@@ -385,7 +386,11 @@ class TrainStep:
         self._dropouts = [m for m in model.modules()
                           if isinstance(m, torch.nn.Dropout) and m.p > 0.0] \
             if dev.type == "cuda" else []
-        if self._dropouts:
+        # simplex dropout (nn.SimplexDropout) draws from the same state: the one
+        # advance per step, the rank seeds and the checkpointed counter serve both
+        self._simplex = [m for m in model.modules() if isinstance(m, SimplexDropout)] \
+            if dev.type == "cuda" else []
+        if self._dropouts or self._simplex:
             if self.world > 1:
                 ops.dropout_set_rank(dist.get_rank(), dev)
             else:
@@ -404,9 +409,11 @@ class TrainStep:
         """Start of a step: zero the gradient bucket.  With the HIP Adam the
         step count is incremented in the same launch (hlhgat_adam_prepare);
         returns whether it was (the update then must not count again).  A
-        model with a live Dropout also advances the dropout step here (one
-        more launch; captured, it draws fresh masks on every replay)."""
-        if self._dropouts and ops.HIP_DROPOUT and any(m.training for m in self._dropouts):
+        model with a live Dropout or SimplexDropout also advances the dropout
+        step here (one more launch for both kinds; captured, they draw fresh
+        masks on every replay)."""
+        if (self._dropouts and ops.HIP_DROPOUT and any(m.training for m in self._dropouts)) \
+                or any(m.training for m in self._simplex):
             ops.dropout_advance(self.device)
         if self._hip_adam:
             ops.adam_prepare(self.flat_grad, self.opt.state[self.master]["step"])
@@ -984,7 +991,7 @@ class TrainStep:
         sd = {"model": self.model.state_dict(), "opt": self.opt.state_dict()}
         if self._hip_adam:  # a snapshot, not the live scalar later fills would change
             sd["opt"]["param_groups"][0]["lr"] = self._lr_dev.detach().clone()
-        if self._dropouts and ops.HIP_DROPOUT:
+        if (self._dropouts and ops.HIP_DROPOUT) or self._simplex:
             seed, step, site = ops.dropout_state(self.device)
             sd["dropout"] = (seed, step)
             sd["dropout_site"] = site
@@ -1037,7 +1044,7 @@ class TrainStep:
                 self._lr_dev.fill_(float(groups[0]["lr"]))
             if "initial_lr" in groups[0]:  # left by a scheduler; its own state is the caller's
                 self.opt.param_groups[0]["initial_lr"] = groups[0]["initial_lr"]
-        if "dropout" in sd and self._dropouts:
+        if "dropout" in sd and (self._dropouts or self._simplex):
             seed, step = sd["dropout"]
             ops.dropout_set_state(seed, step, self.device, site=sd.get("dropout_site", 0))
 

@@ -1226,6 +1226,51 @@ int hlhgat_dropout_bwd(const float* dy, int64_t lddy, int64_t n, int64_t d, uint
 /* state[1] += 1 (one thread): the next step's masks.  Capturable. */
 int hlhgat_dropout_advance(int64_t* state, void* stream);
 
+/* ---- simplex dropout: masked Hodge operators ---------------------------- */
+/* The draw of dropout_node (main_TSP_HL_HGCNN_dense_int3_pyr.py:84-92: the
+ * per-sample rate p + U/2, prob > rate, logical_or with y_loc) together with
+ * the per-sample coin of TSP_EigPE.get (:125-131 == lib/Hodge_Dataset.py:
+ * 696-701), for every graph of a batch in one launch, and the mask column
+ * the reference appends to x_s (:138 == lib/Hodge_Dataset.py:707).
+ * Counter-based like hlhgat_dropout_fwd: state = {seed, step} (two int64,
+ * device) is read by the kernel, nothing is stored between steps.
+ *   graph g (rows seg_ptr[g] .. seg_ptr[g+1]):
+ *     (a0, a1, ., .) = philox4x32-10({g, 0, site, step lo}, {seed lo, seed hi})
+ *     aug_g = (a0 >> 8) < Ta;   T_g = Tp + ((uint64(a1 >> 8) * Tj) >> 24)
+ *   row e of graph g:
+ *     u_e = word (e & 3) of philox({(e>>2) lo, (e>>2) hi, site + 1, step lo},
+ *           key) >> 8
+ *     keep_e = !aug_g || u_e >= T_g || protect[e * ldp] != 0
+ *   rows in no graph (e >= seg_ptr[n_graphs], static-shape padding): 0.
+ * Ta = floor(aug_prob 2^24), Tp = floor(p 2^24), Tj = floor(jitter 2^24), all
+ * <= 2^24 and Tp + Tj <= 2^24; site = 0x80000000 + 2k (k: the caller's module
+ * ordinal; the feature dropout's call counters never reach bit 31).  seg_ptr
+ * is int32 [n_graphs + 1], ascending; protect (optional) is read at stride
+ * ldp.  mask [n_rows] receives 1.0 / 0.0; col (optional) receives the same
+ * values at stride ldc (x_s[:, 1]).  n_rows == 0 is a no-op. */
+int hlhgat_simplex_keep(const int32_t* seg_ptr, int64_t n_graphs, int64_t n_rows,
+                        const float* protect, int64_t ldp, uint32_t Ta, uint32_t Tp, uint32_t Tj,
+                        uint32_t site, const int64_t* state, float* mask, float* col,
+                        int64_t ldc, void* stream);
+/* subgraph(node_mask, edge_index_s, edge_weight_s) without relabelling
+ * (main_TSP_HL_HGCNN_dense_int3_pyr.py:93-95 == lib/Hodge_Dataset.py:163-165)
+ * on a CSR operator whose structure stays: val_out[e] = val[e] if mask[row of
+ * e] and mask[col[e]] are both non-zero, else 0 -- the values of M A M,
+ * M = diag(mask), on A's own rowptr / col.  The SpMM and polynomial-step
+ * entry points on (rowptr, col, val_out) return exactly what they return on
+ * the filtered operator.  n_rows == 0 or nnz == 0 is a no-op. */
+int hlhgat_mask_csr_values(const int32_t* rowptr, const int32_t* col, const float* val,
+                           int64_t n_rows, int64_t nnz, const float* mask, float* val_out,
+                           void* stream);
+/* The same filter (:93-95) on a factored L1 = alpha B1^T B1: sign_out[k] =
+ * node_sign[k] if mask[node_edge[k]] != 0 else 0 (incidence order, [2 n_edges])
+ * and alpha_out[e] = alpha[e] if mask[e] != 0 else 0; the factor with these
+ * two tables in place of node_sign / alpha is M L1 M.  One launch; only
+ * node_edge, node_sign, alpha and n_edges of *f are read.  n_edges == 0 is a
+ * no-op. */
+int hlhgat_mask_hodge_factor(const hlhgat_hodge_factor_t* f, const float* mask, float* sign_out,
+                             float* alpha_out, void* stream);
+
 /* ---- brain input: z-scored series and functional connectivity ----------- */
 /* The per-sample arithmetic of Brain_MLGC_ALL.get (HL-HGAT-DEMO/lib/
  * Hodge_Dataset.py:130-145) and of the cohort loop that feeds FC2mask
