@@ -59,6 +59,8 @@ struct EigArgs {
   double* ws;  // [n_graphs][ws_per_graph] for graphs that miss the LDS
   int64_t ws_per_graph;
   int64_t n_graphs;
+  int64_t max_nodes;  // the caller's bound on a graph's nodes (sizes ws_per_graph)
+  unsigned* err;      // device error word (HLHGAT_DEVERR_EIGPE_SIZE)
 };
 
 __device__ __forceinline__ double wsum(double v) {
@@ -444,6 +446,19 @@ __global__ __launch_bounds__(kEpThreads) void k_eig_pe(EigArgs a) {
       if (threadIdx.x == 0) a.lmax[g] = 0.0;
       continue;
     }
+    if (n > a.max_nodes) {
+      // larger than the caller's max_nodes (device counts: the host could not
+      // check): the workspace slice may not hold it.  Zero rows, lmax 0, and
+      // HLHGAT_DEVERR_EIGPE_SIZE; nothing else is touched for this graph.
+      for (int64_t t = threadIdx.x; t < (int64_t)n * (a.k - 1); t += kEpThreads)
+        a.pe[(n0 + t / (a.k - 1)) * a.ldpe + t % (a.k - 1)] = 0.0f;
+      if (threadIdx.x == 0) {
+        a.lmax[g] = 0.0;
+        if (a.err) __hip_atomic_store(a.err, (unsigned)HLHGAT_DEVERR_EIGPE_SIZE, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      continue;
+    }
     const int nnz = a.inc_rowptr[n0 + n] - a.inc_rowptr[n0];
     if (small_bytes(n, nnz, a.k) <= kEpLdsBytes)
       eig_pe_graph<true>(a, (int)g, n0, n, ep_lds, red, lam, clus);
@@ -515,6 +530,8 @@ extern "C" int hlhgat_eig_pe(const int32_t* inc_rowptr, const int32_t* inc_edge,
   a.ws = reinterpret_cast<double*>(workspace);
   a.ws_per_graph = per_graph_doubles(max_nodes, k);
   a.n_graphs = n_graphs;
+  a.max_nodes = max_nodes;
+  a.err = device_error_word();
   const int64_t grid = eig_pe_grid(n_graphs);
   hipLaunchKernelGGL(k_eig_pe, dim3((unsigned)grid), dim3(kEpThreads), kEpLdsBytes,
                      as_stream(stream), a);

@@ -9,7 +9,8 @@
 // list and the incidence CSR alone:
 //   * k_lanczos_lmax: lmax of every graph's L0 in ONE launch, one
 //     wave per graph: Lanczos on L0 x = deg .* x - A x (fp64, three-term
-//     recurrence with local re-orthogonalisation, <= 64 steps), then the
+//     recurrence with local re-orthogonalisation, min(n, steps) steps with
+//     steps <= 1024, 64 by default), then the
 //     largest eigenvalue of the tridiagonal matrix by Sturm-sequence bisection;
 //   * k_hodge_l0_rows / k_hodge_l1_rows: the sparse L0 / L1 rows in CSR
 //     (columns ascending, as dense_to_sparse orders them) with the
@@ -26,7 +27,7 @@ using namespace hlhgat;
 namespace {
 
 constexpr int kLzThreads = 64;          // one wave per graph
-constexpr int kLzMaxSteps = 64;
+constexpr int kLzMaxSteps = 1024;        // al, be: 16 KB of static LDS beside the 48 KB
 constexpr int kLzLdsBytes = 48 * 1024;  // a graph's vectors + local adjacency, when they fit
 
 struct LanczosArgs {
@@ -124,7 +125,7 @@ __device__ int lanczos(Apply apply, int n, int m, double* qp, double* q, double*
 // memory with its vectors in the workspace.
 __global__ __launch_bounds__(kLzThreads) void k_lanczos_lmax(LanczosArgs a) {
   extern __shared__ __align__(16) unsigned char lz_lds[];
-  __shared__ double al[kLzMaxSteps + 1], be[kLzMaxSteps + 2];
+  __shared__ double al[kLzMaxSteps], be[kLzMaxSteps];  // al[0 .. m-1], be[1 .. m-1]
   const int g = blockIdx.x;
   const int lane = threadIdx.x;
   const int64_t n0 = a.node_ptr[g], n1 = a.node_ptr[g + 1];

@@ -232,6 +232,7 @@ DEVERR_HODGE_SIZE = 2
 DEVERR_LABEL = 4
 DEVERR_METRIC_LABEL = 8
 DEVERR_METER_FULL = 16
+DEVERR_EIGPE_SIZE = 32
 LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
 CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
 LOSS_ONE_LAUNCH_MAX = 16384  # up to here the loss forwards need no workspace

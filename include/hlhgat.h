@@ -382,12 +382,22 @@ int hlhgat_poly_basis_bwd_factored(int kind, const hlhgat_hodge_factor_t* f, int
  * hlhgat_hodge_lmax: lmax of every graph's L0 = B1 B1^T (graph g = nodes
  * [node_ptr[g], node_ptr[g+1])), one wave per graph (vectors and the local
  * adjacency in LDS when they fit in 48 KB), fp64 Lanczos by the three-term
- * recurrence with local re-orthogonalisation (`steps` <= 64 iterations; the
- * largest Ritz value converges first and loss of orthogonality only adds
- * ghost copies) and Sturm bisection of the tridiagonal matrix.  Workspace:
- * 3 n_nodes doubles (the vectors of graphs that miss the LDS).  The
- * reference's float32 eigh agrees to its own rounding (~1e-7 relative), so
- * entries built from this lmax may differ from the reference's by an ulp. */
+ * recurrence with local re-orthogonalisation (min(n, steps) iterations,
+ * 1 <= steps <= 1024; the largest Ritz value converges first and loss of
+ * orthogonality only adds ghost copies) and Sturm bisection of the
+ * tridiagonal matrix.  Workspace: 3 n_nodes doubles (the vectors of graphs
+ * that miss the LDS).
+ * Accuracy against a dense fp64 eigh (tests/test_hodge_lmax.py):
+ * the result is a Ritz value, so it never exceeds lmax; a graph with
+ * n <= steps nodes is exact to fp64 rounding.  At steps = 64 the workloads'
+ * kNN graphs (k = 8 .. 25, any size, with edge dropout) and grids up to
+ * 20 x 20 agree to ~1e-14 relative, chain-like trees of up to ~450 nodes
+ * to 1e-7 or better -- inside the reference's own float32 eigh rounding (~1e-7), so
+ * entries built from this lmax differ from the reference's by an ulp at most.
+ * Slowly mixing graphs do NOT converge in 64 steps: a path of 100 .. 1000
+ * nodes or a ring of 444 .. 1000 is off by ~1e-4, a 30 x 30 grid by 2e-6.  Such
+ * graphs (path-like, large lattices) need steps ~ n; steps = min(n, 1024)
+ * gives 1e-7 or better on them. */
 int64_t hlhgat_hodge_lmax_workspace_bytes(int64_t n_nodes, int steps);
 int hlhgat_hodge_lmax(const int32_t* inc_rowptr, const int32_t* inc_edge,
                       const int64_t* edge_index, int64_t n_edges, int64_t n_nodes,
@@ -408,7 +418,9 @@ int hlhgat_hodge_lmax(const int32_t* inc_rowptr, const int32_t* inc_edge,
  * are defined up to sign (and rotation within equal eigenvalues).
  * max_nodes >= every graph's node count (sizes the workspace slice a graph
  * too large for the LDS uses: one slice per workgroup, min(n_graphs, CUs)
- * workgroups, so the size depends on the current device); 2 <= k <= 64. */
+ * workgroups, so the size depends on the current device); 2 <= k <= 64.
+ * A graph with more than max_nodes nodes is not computed: its pe rows are
+ * zero, its lmax is 0 and HLHGAT_DEVERR_EIGPE_SIZE is raised. */
 int64_t hlhgat_eig_pe_workspace_bytes(int64_t n_graphs, int64_t max_nodes, int k);
 int hlhgat_eig_pe(const int32_t* inc_rowptr, const int32_t* inc_edge, const int64_t* edge_index,
                   int64_t n_edges, int64_t n_nodes, const int64_t* node_ptr, int64_t n_graphs,
@@ -1071,6 +1083,9 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
 #define HLHGAT_DEVERR_METRIC_LABEL 8u
 /* hlhgat_collect_rows: the rows did not fit the buffer; none was appended */
 #define HLHGAT_DEVERR_METER_FULL 16u
+/* hlhgat_eig_pe: a graph has more nodes than the caller's max_nodes (which
+ * sized its workspace slice); its pe rows are zero and its lmax is 0 */
+#define HLHGAT_DEVERR_EIGPE_SIZE 32u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 
