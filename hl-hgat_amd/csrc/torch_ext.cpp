@@ -20,8 +20,10 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
 #include <algorithm>
+#include <cstring>
 #include <mutex>
 #include <optional>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -63,30 +65,88 @@ inline void req(const Tensor& t, const char* name) {
 // needs_input_grad() indexes EDGES: a Tensor argument is always an edge, an
 // optional<Tensor> only when defined, each TensorList element is one, and any
 // other argument none.  Backward still returns one gradient per position.
+//
+// A node's forward walks its arguments ONCE, in signature order, through an
+// EdgeMap: each call returns the position it was given, which the node keeps
+// in a struct of named positions (its `Pos`).  The backward reads both back
+// (Edges<Pos>), asks need(pos.name), and sizes its result from the map.
 struct EdgeMap {
   std::vector<int64_t> e;
   int64_t n = 0;
-  void tensor() { e.push_back(n++); }
-  void opt(const OptT& t) { e.push_back(has(t) ? n++ : -1); }
-  void list(at::TensorList l) {
-    for (size_t i = 0; i < l.size(); ++i) e.push_back(n++);
+  // `count` consecutive arguments of one kind: the position of the first
+  int64_t put(bool edge, size_t count = 1) {
+    for (size_t i = 0; i < count; ++i) e.push_back(edge ? n++ : -1);
+    return (int64_t)(e.size() - count);
   }
-  void other() { e.push_back(-1); }
+  int64_t tensor(size_t count = 1) { return put(true, count); }
+  int64_t opt(const OptT& t) { return put(has(t)); }
+  int64_t other(size_t count = 1) { return put(false, count); }
+  int64_t list(at::TensorList l) { return put(true, l.size()); }  // l[i] is at + i
 };
-inline bool need(AutogradContext* ctx, int64_t pos) {
-  const auto em = ctx->saved_data["edges"].toIntVector();
-  return pos < (int64_t)em.size() && em[pos] >= 0 && ctx->needs_input_grad(em[pos]);
+
+// A struct of int64_t fields only (positions, sizes) <-> saved_data's IntVector.
+template <class P>
+std::vector<int64_t> pod_ints(const P& p) {
+  static_assert(std::is_trivially_copyable<P>::value && sizeof(P) % sizeof(int64_t) == 0,
+                "a struct of int64_t fields");
+  std::vector<int64_t> v(sizeof(P) / sizeof(int64_t));
+  std::memcpy(v.data(), &p, sizeof(P));
+  return v;
+}
+template <class P>
+P ints_pod(const std::vector<int64_t>& v) {
+  TORCH_INTERNAL_ASSERT(v.size() * sizeof(int64_t) == sizeof(P));
+  P p;
+  std::memcpy(&p, v.data(), sizeof(P));
+  return p;
+}
+
+template <class P>
+void save_edges(AutogradContext* ctx, const EdgeMap& em, const P& pos) {
+  ctx->saved_data["edges"] = em.e;
+  ctx->saved_data["pos"] = pod_ints(pos);
+}
+template <class P>
+struct Edges {  // the forward's walk, read once per backward
+  AutogradContext* ctx;
+  std::vector<int64_t> e;
+  P pos;
+  explicit Edges(AutogradContext* c)
+      : ctx(c), e(c->saved_data["edges"].toIntVector()),
+        pos(ints_pod<P>(c->saved_data["pos"].toIntVector())) {}
+  bool need(int64_t p) const { return e[p] >= 0 && ctx->needs_input_grad(e[p]); }
+  std::vector<bool> need(int64_t first, size_t n) const {  // of a list argument
+    std::vector<bool> nd;
+    for (size_t i = 0; i < n; ++i) nd.push_back(need(first + (int64_t)i));
+    return nd;
+  }
+  variable_list grads() const { return variable_list(e.size()); }  // one per position
+};
+
+inline Tensor opt_or_undef(const OptT& t) { return has(t) ? *t : Tensor(); }
+inline OptT undef_to_opt(const Tensor& t) { return t.defined() ? OptT(t) : OptT(); }
+inline Tensor row_major(const Tensor& W) { return W.stride(1) == 1 ? W : W.contiguous(); }
+
+// Saved tensors by name: a node's `Saved` struct lists its fixed fields once
+// (slots()); a variable-length tail follows them (load_slots returns it).
+template <class S>
+void save_slots(AutogradContext* ctx, S& s, const std::vector<Tensor>& tail = {}) {
+  variable_list v;
+  for (Tensor* t : s.slots()) v.push_back(*t);
+  v.insert(v.end(), tail.begin(), tail.end());
+  ctx->save_for_backward(v);
+}
+template <class S>
+std::vector<Tensor> load_slots(AutogradContext* ctx, S& s) {
+  const variable_list v = ctx->get_saved_variables();
+  auto it = v.begin();
+  for (Tensor* t : s.slots()) *t = *it++;
+  return {it, v.end()};
 }
 
 // ---------------------------------------------------------------------------
 // raw launches
 // ---------------------------------------------------------------------------
-struct Csr {
-  Tensor rowptr, col;
-  OptT val;
-  int64_t nnz;
-};
-
 // hlhgat_halo_t over the halo-tile tensors of an operator (see hlhgat.h);
 // bounds = {max_halo, max_rows, max_nnz}
 hlhgat_halo_t make_halo(const Tensor& tile, const Tensor& ptr, const Tensor& cols,
@@ -274,20 +334,6 @@ void proj_fwd(const std::vector<const float*>& A, const std::vector<int64_t>& ld
       "proj_fwd");
 }
 
-void proj_bwd_weight(const Tensor& G, const std::vector<const float*>& A,
-                     const std::vector<int64_t>& lda, const std::vector<int64_t>& kb,
-                     std::vector<float*>& dW, const std::vector<int64_t>& lddw, float* db,
-                     void* s) {
-  const int nb = (int)A.size();
-  const int64_t M = G.size(0), N = G.size(1);
-  const int64_t wsf =
-      hlhgat_proj_bwd_weight_workspace_floats(nb, kb.data(), M, N, db != nullptr);
-  Tensor ws = at::empty({std::max<int64_t>(wsf, 1)}, G.options());
-  chk(hlhgat_proj_bwd_weight(nb, G.data_ptr<float>(), ld_of(G), A.data(), lda.data(), kb.data(),
-                             M, N, dW.data(), lddw.data(), db, 0, ws.data_ptr<float>(), wsf, s),
-      "proj_bwd_weight");
-}
-
 // set_fused_bwd(false) (tests): weight and data gradients as separate
 // launches instead of hlhgat_proj_bwd's single launch (bitwise the same).
 bool& fused_bwd_flag() {
@@ -463,26 +509,36 @@ std::vector<int64_t> reduce_flush(int64_t device) {
   return out;
 }
 
+// The operands of one Linear's weight (+ bias) gradient, dW_b = G^T A_b, and
+// of its data gradient, dA_b (+)= G W_b (acc = 1: added into dA_b).
+struct GradW {
+  std::vector<const float*> A;
+  std::vector<int64_t> lda, kb, lddw;
+  std::vector<float*> dW;
+  float* db = nullptr;
+  std::vector<Tensor> out;  // the tensors dW / db point into (zero-filled when M == 0)
+};
+struct GradD {
+  std::vector<const float*> W;
+  std::vector<int64_t> ldw, kb, ldda;
+  std::vector<float*> dA;
+  int acc = 0;
+};
+
 // weight (+bias) and data gradients of one Linear: hlhgat_proj_bwd (weight
 // partials and data gradient in one launch, then the split reduction)
-void proj_bwd_both(const Tensor& G, const std::vector<const float*>& A,
-                   const std::vector<int64_t>& lda, const std::vector<int64_t>& kbw,
-                   std::vector<float*>& dW, const std::vector<int64_t>& lddw, float* db,
-                   const std::vector<const float*>& W, const std::vector<int64_t>& ldw,
-                   const std::vector<int64_t>& kbd, std::vector<float*>& dA,
-                   const std::vector<int64_t>& ldda, void* s, int acc_d = 0,
-                   bool force_defer = false) {
-  const int nbw = (int)A.size(), nbd = (int)W.size();
+void proj_bwd_both(const Tensor& G, GradW& w, GradD& dd, void* s, bool force_defer) {
+  const int nbw = (int)w.A.size(), nbd = (int)dd.W.size();
   const int64_t M = G.size(0), N = G.size(1);
   const int64_t wsf =
-      nbw ? hlhgat_proj_bwd_weight_workspace_floats(nbw, kbw.data(), M, N, db != nullptr) : 0;
+      nbw ? hlhgat_proj_bwd_weight_workspace_floats(nbw, w.kb.data(), M, N, w.db != nullptr) : 0;
   Tensor ws = at::empty({std::max<int64_t>(wsf, 1)}, G.options());
   auto& d = defer_state();
   std::unique_lock<std::mutex> g(d.mu);
   // force_defer: private gradient buffers read only by deferred copies (the
   // NodeEdgeInt unpack), which the flush runs after every reduction
-  bool defer = d.on && nbw > 0 && (force_defer || deferred_ok(db));
-  for (int b = 0; b < nbw && defer && !force_defer; ++b) defer = deferred_ok(dW[b]);
+  bool defer = d.on && nbw > 0 && (force_defer || deferred_ok(w.db));
+  for (int b = 0; b < nbw && defer && !force_defer; ++b) defer = deferred_ok(w.dW[b]);
   auto it = d.pending.find(s);
   PendingReduce prev;
   const bool merge = it != d.pending.end();
@@ -492,27 +548,37 @@ void proj_bwd_both(const Tensor& G, const std::vector<const float*>& A,
   }
   hlhgat_reduce_desc_t out;
   int deferred = 0;
-  chk(hlhgat_proj_bwd_defer(M, N, G.data_ptr<float>(), ld_of(G), nbw, A.data(), lda.data(),
-                              kbw.data(), dW.data(), lddw.data(), db, nbd, W.data(), ldw.data(),
-                              kbd.data(), dA.data(), ldda.data(), acc_d, ws.data_ptr<float>(),
-                              wsf, merge ? &prev.desc : nullptr, defer ? &out : nullptr,
-                              &deferred, s),
+  chk(hlhgat_proj_bwd_defer(M, N, G.data_ptr<float>(), ld_of(G), nbw, w.A.data(), w.lda.data(),
+                              w.kb.data(), w.dW.data(), w.lddw.data(), w.db, nbd, dd.W.data(),
+                              dd.ldw.data(), dd.kb.data(), dd.dA.data(), dd.ldda.data(), dd.acc,
+                              ws.data_ptr<float>(), wsf, merge ? &prev.desc : nullptr,
+                              defer ? &out : nullptr, &deferred, s),
         "proj_bwd");
   if (merge || deferred) d.streams.insert(s);
   if (deferred) {
     d.pending[s] = PendingReduce{out, ws, s};
-    for (int b = 0; b < nbw; ++b) d.dests.insert(dW[b]);
-    if (db) d.dests.insert(db);
+    for (int b = 0; b < nbw; ++b) d.dests.insert(w.dW[b]);
+    if (w.db) d.dests.insert(w.db);
   }
 }
 
-void proj_bwd_data(const Tensor& G, const std::vector<const float*>& W,
-                   const std::vector<int64_t>& ldw, const std::vector<int64_t>& kb,
-                   std::vector<float*>& dA, const std::vector<int64_t>& ldda, void* s,
-                   int acc = 0) {
-  chk(hlhgat_proj_bwd_data((int)W.size(), G.data_ptr<float>(), ld_of(G), W.data(), ldw.data(),
-                           kb.data(), G.size(0), G.size(1), dA.data(), ldda.data(), acc, s),
-      "proj_bwd_data");
+// The launches for the gradients of one Linear given G [M, N]; either set may
+// be absent.  Both in ONE launch, else the weight gradient alone (the
+// one-launch path with no data items) and / or the data gradient alone.
+void linear_grads(const Tensor& G, GradW* w, GradD* d, void* s, bool force_defer = false) {
+  if (G.size(0) == 0) {
+    if (w)
+      for (auto& t : w->out) t.zero_();
+    return;
+  }
+  const bool both = w && d && fused_bwd_flag();
+  GradD none;
+  if (w) proj_bwd_both(G, *w, both ? *d : none, s, both && force_defer);
+  if (d && !both)
+    chk(hlhgat_proj_bwd_data((int)d->W.size(), G.data_ptr<float>(), ld_of(G), d->W.data(),
+                             d->ldw.data(), d->kb.data(), G.size(0), G.size(1), d->dA.data(),
+                             d->ldda.data(), d->acc, s),
+        "proj_bwd_data");
 }
 
 struct BnState {
@@ -587,10 +653,6 @@ Tensor bn_backward(const Tensor& x, const OptT& y, const Tensor& dy, const OptT&
                           ws.numel(), stream_of(x)),
       "bn_bwd_train");
   return dx;
-}
-
-inline bool al4(const void* p, int64_t ld) {
-  return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0;
 }
 
 // Two-stream fork inside one autograd node: the node (current) stream and a
@@ -671,43 +733,78 @@ struct ConvArgs {
   int64_t fac_nodes = 0;
 };
 
-// What one side's backward needs: the tensors (kSavedFixed, then W[0..K),
-// then the factor) and the sizes.
-constexpr size_t kSavedFixed = 21;
+// What the backward needs: the tensors (the fixed ones, then W[0..K), then the
+// factor) and the sizes.
+struct ConvDims {
+  int64_t N, Cin, F, M, dout, K, kind, nnz, bn_mode, fac_nodes;
+};
 struct ConvSaved {
-  std::vector<Tensor> t;
-  std::vector<int64_t> dims;  // N, Cin, F, M, dout, K, kind, nnz, bn_mode, has_bias
+  Tensor x2, T, t_order, valid, t_rowptr, t_col, t_val, pre, yout, mean, invstd, bn_w, bias,
+      bn_b, h_tile, h_ptr, h_cols, h_srp, h_lcol, h_sval, h_hdr;
+  std::vector<Tensor> W, fac;
+  ConvDims d{};
   std::vector<int64_t> xshape, h_bounds;
-  int64_t fac_nodes = 0;
-  void to_ctx(AutogradContext* ctx, const std::string& p) const {
-    ctx->saved_data[p + "dims"] = dims;
-    ctx->saved_data[p + "xshape"] = xshape;
-    ctx->saved_data[p + "h_bounds"] = h_bounds;
-    ctx->saved_data[p + "misc"] = std::vector<int64_t>{fac_nodes, (int64_t)t.size()};
+  std::vector<Tensor*> slots() {
+    return {&x2, &T, &t_order, &valid, &t_rowptr, &t_col, &t_val, &pre, &yout, &mean, &invstd,
+            &bn_w, &bias, &bn_b, &h_tile, &h_ptr, &h_cols, &h_srp, &h_lcol, &h_sval, &h_hdr};
   }
-  static ConvSaved from_ctx(AutogradContext* ctx, const std::string& p,
-                            const std::vector<Tensor>& all, size_t first) {
+  void save(AutogradContext* ctx) {
+    ctx->saved_data["dims"] = pod_ints(d);
+    ctx->saved_data["xshape"] = xshape;
+    ctx->saved_data["h_bounds"] = h_bounds;
+    std::vector<Tensor> tail = W;
+    tail.insert(tail.end(), fac.begin(), fac.end());
+    save_slots(ctx, *this, tail);
+  }
+  static ConvSaved load(AutogradContext* ctx) {
     ConvSaved s;
-    s.dims = ctx->saved_data[p + "dims"].toIntVector();
-    s.xshape = ctx->saved_data[p + "xshape"].toIntVector();
-    s.h_bounds = ctx->saved_data[p + "h_bounds"].toIntVector();
-    const auto m = ctx->saved_data[p + "misc"].toIntVector();
-    s.fac_nodes = m[0];
-    s.t.assign(all.begin() + first, all.begin() + first + m[1]);
+    s.d = ints_pod<ConvDims>(ctx->saved_data["dims"].toIntVector());
+    s.xshape = ctx->saved_data["xshape"].toIntVector();
+    s.h_bounds = ctx->saved_data["h_bounds"].toIntVector();
+    s.fac = load_slots(ctx, s);  // W[0..K), then the factor
+    s.W.assign(s.fac.begin(), s.fac.begin() + s.d.K);
+    s.fac.erase(s.fac.begin(), s.fac.begin() + s.d.K);
     return s;
   }
 };
 
-// Which gradients one side's backward must produce.
-struct ConvNeeds {
-  bool x = false;
-  std::vector<bool> w;
-  bool bias = false, bn_w = false, bn_b = false;
+// conv_bn's arguments in signature order: the edge map and the positions the
+// backward names
+struct ConvPos {
+  int64_t x, W0, bias, bn_w, bn_b;  // W[k] is at W0 + k
 };
-struct ConvGrads {
-  Tensor dx, dbias, dbn_w, dbn_b;
-  std::vector<Tensor> dW;
-};
+ConvPos walk_conv(EdgeMap& em, const ConvArgs& c) {
+  ConvPos p;
+  p.x = em.tensor();
+  em.tensor(2);  // a_rowptr, a_col
+  em.opt(c.a_val);
+  em.tensor(2);  // t_rowptr, t_col
+  em.opt(c.t_val);
+  em.other(2);  // nnz, kind
+  p.W0 = em.list(c.W);
+  p.bias = em.opt(c.bias);
+  p.bn_w = em.opt(c.bn_w);
+  p.bn_b = em.opt(c.bn_b);
+  em.opt(c.bn_rm);
+  em.opt(c.bn_rv);
+  em.opt(c.bn_nbt);
+  em.other(3);  // momentum, eps, bn_mode
+  em.opt(c.out_buf);
+  em.opt(c.a_order);
+  em.opt(c.t_order);
+  em.opt(c.valid);
+  em.opt(c.h_tile);
+  em.opt(c.h_ptr);
+  em.opt(c.h_cols);
+  em.opt(c.h_srp);
+  em.opt(c.h_lcol);
+  em.opt(c.h_sval);
+  em.other();  // h_bounds
+  em.opt(c.h_hdr);
+  em.list(c.fac);
+  em.other();  // fac_nodes
+  return p;
+}
 
 // HodgeLaguerreConv / HodgeChebConv forward (+ BN (+ ReLU)) of one side.
 Tensor conv_forward(const ConvArgs& c, ConvSaved& sv) {
@@ -765,221 +862,129 @@ Tensor conv_forward(const ConvArgs& c, ConvSaved& sv) {
                     c.out_buf->stride(1) == 1 && c.out_buf->device() == x.device(),
                 "hlhgat: conv output buffer must be a row-major [", M, ", ", dout, "] view");
   Tensor pre = (sink && c.bn_mode == 0) ? *c.out_buf : at::empty({M, dout}, x.options());
-  Tensor out = pre, mean, invstd;
+  Tensor out = pre;
+  const BnState st{c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, c.bn_nbt, c.momentum, c.eps, c.valid};
   if (M > 0 && c.bn_mode > 0) {
-    BnState st{c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, c.bn_nbt, c.momentum, c.eps, c.valid};
     out = proj_bn_forward(Ap, lda, Wp, ldw, kb, M, dout, fptr(c.bias), pre, st, c.bn_mode == 2,
-                          mean, invstd, sink ? &*c.out_buf : nullptr);
+                          sv.mean, sv.invstd, sink ? &*c.out_buf : nullptr);
   } else {
     if (M > 0) {
       proj_fwd(Ap, lda, Wp, ldw, kb, M, dout, fptr(c.bias), pre, s);
     } else if (has(c.bias)) {
       pre.copy_(c.bias->expand_as(pre));
     }
-    if (c.bn_mode > 0) {
-      BnState st{c.bn_w, c.bn_b, c.bn_rm, c.bn_rv, c.bn_nbt, c.momentum, c.eps, c.valid};
-      out = bn_forward(pre, st, c.bn_mode == 2, mean, invstd, sink ? &*c.out_buf : nullptr);
-    }
+    if (c.bn_mode > 0)
+      out = bn_forward(pre, st, c.bn_mode == 2, sv.mean, sv.invstd,
+                       sink ? &*c.out_buf : nullptr);
   }
-  sv.dims = {N, Cin, F, M, dout, K, c.kind, c.nnz, c.bn_mode, has(c.bias) ? 1 : 0};
-  sv.fac_nodes = c.fac_nodes;
+  sv.d = {N, Cin, F, M, dout, K, c.kind, c.nnz, c.bn_mode, c.fac_nodes};
   sv.h_bounds = c.h_bounds;
   sv.xshape = x.sizes().vec();
-  const bool halo_bwd = use_halo && c.t_rowptr.data_ptr() == c.a_rowptr.data_ptr();
-  sv.t = {x2,
-          T,
-          has(c.t_order) ? *c.t_order : Tensor(),
-          has(c.valid) ? *c.valid : Tensor(),
-          c.t_rowptr,
-          c.t_col,
-          has(c.t_val) ? *c.t_val : Tensor(),
-          c.bn_mode > 0 ? pre : Tensor(),
-          c.bn_mode == 2 ? out : Tensor(),
-          mean,
-          invstd,
-          has(c.bn_w) ? *c.bn_w : Tensor(),
-          has(c.bias) ? *c.bias : Tensor(),
-          has(c.bn_b) ? *c.bn_b : Tensor(),
-          halo_bwd ? *c.h_tile : Tensor(),
-          halo_bwd ? *c.h_ptr : Tensor(),
-          halo_bwd ? *c.h_cols : Tensor(),
-          halo_bwd ? *c.h_srp : Tensor(),
-          halo_bwd ? *c.h_lcol : Tensor(),
-          (halo_bwd && has(c.h_sval)) ? *c.h_sval : Tensor(),
-          halo_bwd ? *c.h_hdr : Tensor()};
-  for (const auto& w : c.W) sv.t.push_back(w);
-  for (const auto& t : c.fac) sv.t.push_back(t);
+  sv.x2 = x2;
+  sv.T = T;
+  sv.t_order = opt_or_undef(c.t_order);
+  sv.valid = opt_or_undef(c.valid);
+  sv.t_rowptr = c.t_rowptr;
+  sv.t_col = c.t_col;
+  sv.t_val = opt_or_undef(c.t_val);
+  if (c.bn_mode > 0) sv.pre = pre;
+  if (c.bn_mode == 2) sv.yout = out;
+  sv.bn_w = opt_or_undef(c.bn_w);
+  sv.bias = opt_or_undef(c.bias);
+  sv.bn_b = opt_or_undef(c.bn_b);
+  if (use_halo && c.t_rowptr.data_ptr() == c.a_rowptr.data_ptr()) {
+    sv.h_tile = *c.h_tile;
+    sv.h_ptr = *c.h_ptr;
+    sv.h_cols = *c.h_cols;
+    sv.h_srp = *c.h_srp;
+    sv.h_lcol = *c.h_lcol;
+    sv.h_sval = opt_or_undef(c.h_sval);
+    sv.h_hdr = *c.h_hdr;
+  }
+  sv.W = c.W;
+  sv.fac = c.fac;
   std::vector<int64_t> oshape = x.sizes().vec();
   oshape.back() = dout;
   return out.view(oshape);
 }
 
-ConvGrads conv_backward(const ConvSaved& sv, const Tensor& grad, const ConvNeeds& nd) {
-  const auto& d = sv.dims;
-  const int64_t N = d[0], Cin = d[1], F = d[2], M = d[3], dout = d[4], K = d[5], kind = d[6],
-                nnz = d[7], bn_mode = d[8];
-  const bool has_bias = d[9] != 0;
-  const auto& t = sv.t;
-  Tensor x2 = t[0], T = t[1], t_order = t[2], valid = t[3], t_rowptr = t[4], t_col = t[5],
-         t_val = t[6], pre = t[7], yout = t[8], mean = t[9], invstd = t[10], bn_w = t[11],
-         bias_p = t[12], bn_b = t[13], h_tile = t[14], h_ptr = t[15], h_cols = t[16],
-         h_srp = t[17], h_lcol = t[18], h_sval = t[19], h_hdr = t[20];
-  std::vector<Tensor> W(t.begin() + kSavedFixed, t.begin() + kSavedFixed + K);
-  std::vector<Tensor> fac(t.begin() + kSavedFixed + K, t.end());
-  const bool use_halo = h_lcol.defined();
+// one gradient per argument position of conv_bn
+variable_list conv_backward(const ConvSaved& sv, const Tensor& grad, const Edges<ConvPos>& ed) {
+  const ConvDims& d = sv.d;
+  const ConvPos& pos = ed.pos;
+  const int64_t N = d.N, Cin = d.Cin, F = d.F, M = d.M, K = d.K;
+  const Tensor& x2 = sv.x2;
+  const bool use_halo = sv.h_lcol.defined();
   const hlhgat_halo_t halo =
-      use_halo ? make_halo(h_tile, h_ptr, h_cols, h_srp, h_lcol, h_sval, sv.h_bounds, h_hdr)
+      use_halo ? make_halo(sv.h_tile, sv.h_ptr, sv.h_cols, sv.h_srp, sv.h_lcol, sv.h_sval,
+                           sv.h_bounds, sv.h_hdr)
                : hlhgat_halo_t{};
   void* s = stream_of(x2);
   // row-strided is fine (e.g. a column block of the gradient slab)
-  Tensor G = rows2d(grad.reshape({M, dout}));
-  ConvGrads out;
-  out.dW.resize(K);
-  std::vector<const float*> Ap(K);
-  std::vector<int64_t> lda(K), kb(K, Cin);
-  Ap[0] = x2.data_ptr<float>();
-  lda[0] = (int64_t)sv.xshape.size() == 2 ? ld_of(x2) : Cin;
-  for (int64_t k = 1; k < K; ++k) {
-    Ap[k] = T.data_ptr<float>() + (k - 1) * N * F;
-    lda[k] = Cin;
-  }
+  Tensor G = rows2d(grad.reshape({M, d.dout}));
+  variable_list out = ed.grads();
+  const bool need_x = ed.need(pos.x);
   bool need_w = false;
-  for (int64_t k = 0; k < K; ++k) need_w = need_w || nd.w[k];
-  const bool need_b = has_bias && nd.bias;
-  struct {
-    std::vector<float*> dWp;
-    std::vector<int64_t> lddw;
-    float* db = nullptr;
-  } wdef;  // weight gradient deferred into the data gradient's launch
-  if (bn_mode > 0) {
-    const OptT bn_y = bn_mode == 2 ? OptT(yout) : OptT();
-    OptT w = bn_w.defined() ? OptT(bn_w) : OptT();
-    G = bn_backward(pre, bn_y, G, w, mean, invstd, nd.bn_w, nd.bn_b, out.dbn_w, out.dbn_b,
-                    nullptr, &bn_b, valid);
+  for (int64_t k = 0; k < K; ++k) need_w = need_w || ed.need(pos.W0 + k);
+  const bool need_b = ed.need(pos.bias);  // an absent bias is no edge
+  if (d.bn_mode > 0) {
+    const OptT bn_y = d.bn_mode == 2 ? OptT(sv.yout) : OptT();
+    G = bn_backward(sv.pre, bn_y, G, undef_to_opt(sv.bn_w), sv.mean, sv.invstd,
+                    ed.need(pos.bn_w), ed.need(pos.bn_b), out[pos.bn_w], out[pos.bn_b], nullptr,
+                    &sv.bn_b, sv.valid);
   }
+  GradW gw;
   if (need_w || need_b) {
-    std::vector<Tensor> dW(K);
-    std::vector<float*> dWp(K);
-    std::vector<int64_t> lddw(K);
+    gw.A.resize(K);
+    gw.lda = gw.kb = gw.lddw = std::vector<int64_t>(K, Cin);
+    gw.A[0] = x2.data_ptr<float>();
+    if (sv.xshape.size() == 2) gw.lda[0] = ld_of(x2);
+    for (int64_t k = 1; k < K; ++k) gw.A[k] = sv.T.data_ptr<float>() + (k - 1) * N * F;
     for (int64_t k = 0; k < K; ++k) {
-      dW[k] = nd.w[k] ? grad_like(W[k]) : at::empty({dout, Cin}, x2.options());
-      dWp[k] = dW[k].data_ptr<float>();
-      lddw[k] = Cin;
+      const bool nk = ed.need(pos.W0 + k);
+      gw.out.push_back(nk ? grad_like(sv.W[k]) : at::empty({d.dout, Cin}, x2.options()));
+      gw.dW.push_back(gw.out[k].data_ptr<float>());
+      if (nk) out[pos.W0 + k] = gw.out[k];
     }
-    Tensor db = need_b ? grad_like(bias_p) : Tensor();
-    if (M > 0 && nd.x && fused_bwd_flag()) {
-      wdef.dWp = dWp;  // launched with the data gradient
-      wdef.lddw = lddw;
-      wdef.db = need_b ? db.data_ptr<float>() : nullptr;
-    } else if (M > 0) {  // weight only: the one-launch path with no data items
-      std::vector<const float*> noW;
-      std::vector<int64_t> noL;
-      std::vector<float*> noD;
-      proj_bwd_both(G, Ap, lda, kb, dWp, lddw, need_b ? db.data_ptr<float>() : nullptr, noW, noL,
-                    noL, noD, noL, s, 0, false);
-    } else {
-      for (auto& tt : dW) tt.zero_();
-      if (need_b) db.zero_();
+    if (need_b) {
+      out[pos.bias] = grad_like(sv.bias);
+      gw.db = out[pos.bias].data_ptr<float>();
+      gw.out.push_back(out[pos.bias]);
     }
-    for (int64_t k = 0; k < K; ++k)
-      if (nd.w[k]) out.dW[k] = dW[k];
-    if (need_b) out.dbias = db;
   }
-  if (nd.x) {
-    Tensor Gs = at::empty({K, N, F}, x2.options());
-    if (M > 0) {
-      std::vector<const float*> Wp(K);
-      std::vector<int64_t> ldw(K), ldda(K, Cin);
-      std::vector<float*> dA(K);
-      for (int64_t k = 0; k < K; ++k) {
-        Wp[k] = W[k].data_ptr<float>();
-        ldw[k] = W[k].stride(0);
-        dA[k] = Gs.data_ptr<float>() + k * N * F;
-      }
-      if (!wdef.dWp.empty())
-        proj_bwd_both(G, Ap, lda, kb, wdef.dWp, wdef.lddw, wdef.db, Wp, ldw, kb, dA, ldda, s, 0,
-                      false);
-      else
-        proj_bwd_data(G, Wp, ldw, kb, dA, ldda, s);
-      if (K > 1 && !fac.empty()) {  // L1 symmetric: the adjoint uses the same factor
-        const hlhgat_hodge_factor_t hf = make_factor(fac, sv.fac_nodes, N);
-        Tensor work = at::empty({hlhgat_hodge_factor_work_floats(sv.fac_nodes, F)}, x2.options());
-        chk(hlhgat_poly_basis_bwd_factored((int)kind, &hf, F, (int)K, Gs.data_ptr<float>(),
-                                           work.data_ptr<float>(), s),
-            "poly_basis_bwd_factored");
-      } else if (K > 1) {
-        chk(hlhgat_poly_basis_bwd((int)kind, t_rowptr.data_ptr<int>(),
-                                  nnz ? t_col.data_ptr<int>() : nullptr,
-                                  (nnz && t_val.defined()) ? t_val.data_ptr<float>() : nullptr, N,
-                                  nnz, t_order.defined() ? t_order.data_ptr<int>() : nullptr,
-                                  use_halo ? &halo : nullptr, F, (int)K, Gs.data_ptr<float>(), s),
-            "poly_basis_bwd");
-      }
-    } else {
+  GradD gd;
+  Tensor Gs;
+  if (need_x) {
+    Gs = at::empty({K, N, F}, x2.options());
+    gd.kb = gd.ldda = std::vector<int64_t>(K, Cin);
+    for (int64_t k = 0; k < K; ++k) {
+      gd.W.push_back(sv.W[k].data_ptr<float>());
+      gd.ldw.push_back(sv.W[k].stride(0));
+      gd.dA.push_back(Gs.data_ptr<float>() + k * N * F);
+    }
+  }
+  linear_grads(G, (need_w || need_b) ? &gw : nullptr, need_x ? &gd : nullptr, s);
+  if (need_x) {
+    if (M > 0 && K > 1 && !sv.fac.empty()) {  // L1 symmetric: the adjoint uses the same factor
+      const hlhgat_hodge_factor_t hf = make_factor(sv.fac, d.fac_nodes, N);
+      Tensor work = at::empty({hlhgat_hodge_factor_work_floats(d.fac_nodes, F)}, x2.options());
+      chk(hlhgat_poly_basis_bwd_factored((int)d.kind, &hf, F, (int)K, Gs.data_ptr<float>(),
+                                         work.data_ptr<float>(), s),
+          "poly_basis_bwd_factored");
+    } else if (M > 0 && K > 1) {
+      const Tensor &tv = sv.t_val, &to = sv.t_order;
+      chk(hlhgat_poly_basis_bwd((int)d.kind, sv.t_rowptr.data_ptr<int>(),
+                                d.nnz ? sv.t_col.data_ptr<int>() : nullptr,
+                                (d.nnz && tv.defined()) ? tv.data_ptr<float>() : nullptr, N, d.nnz,
+                                to.defined() ? to.data_ptr<int>() : nullptr,
+                                use_halo ? &halo : nullptr, F, (int)K, Gs.data_ptr<float>(), s),
+          "poly_basis_bwd");
+    } else if (M == 0) {
       Gs.zero_();
     }
-    out.dx = Gs[0].view(sv.xshape);
+    out[pos.x] = Gs[0].view(sv.xshape);
   }
   return out;
-}
-
-// argument positions of conv_bn (needs_input_grad / gradient slots)
-constexpr int64_t kConvPosW = 9;  // W[0..K), then bias, bn_w, bn_b
-
-ConvNeeds conv_needs(AutogradContext* ctx, int64_t K, int64_t base) {
-  ConvNeeds nd;
-  nd.x = need(ctx, base);
-  nd.w.resize(K);
-  for (int64_t k = 0; k < K; ++k) nd.w[k] = need(ctx, base + kConvPosW + k);
-  nd.bias = need(ctx, base + kConvPosW + K);
-  nd.bn_w = need(ctx, base + kConvPosW + K + 1);
-  nd.bn_b = need(ctx, base + kConvPosW + K + 2);
-  return nd;
-}
-
-void edge_map_conv(EdgeMap& em, const ConvArgs& c) {
-  em.tensor();  // x
-  em.tensor();
-  em.tensor();
-  em.opt(c.a_val);
-  em.tensor();
-  em.tensor();
-  em.opt(c.t_val);
-  em.other();
-  em.other();
-  em.list(c.W);
-  em.opt(c.bias);
-  em.opt(c.bn_w);
-  em.opt(c.bn_b);
-  em.opt(c.bn_rm);
-  em.opt(c.bn_rv);
-  em.opt(c.bn_nbt);
-  em.other();
-  em.other();
-  em.other();
-  em.opt(c.out_buf);
-  em.opt(c.a_order);
-  em.opt(c.t_order);
-  em.opt(c.valid);
-  em.opt(c.h_tile);
-  em.opt(c.h_ptr);
-  em.opt(c.h_cols);
-  em.opt(c.h_srp);
-  em.opt(c.h_lcol);
-  em.opt(c.h_sval);
-  em.other();
-  em.opt(c.h_hdr);
-  em.list(c.fac);
-  em.other();
-}
-constexpr int64_t conv_positions(int64_t K, int64_t n_fac) { return 30 + K + n_fac + 1; }
-
-void put_grads(variable_list& out, int64_t base, int64_t K, const ConvGrads& g) {
-  out[base] = g.dx;
-  for (int64_t k = 0; k < K; ++k) out[base + kConvPosW + k] = g.dW[k];
-  out[base + kConvPosW + K] = g.dbias;
-  out[base + kConvPosW + K + 1] = g.dbn_w;
-  out[base + kConvPosW + K + 2] = g.dbn_b;
 }
 
 class ConvBNFn : public torch::autograd::Function<ConvBNFn> {
@@ -1000,20 +1005,13 @@ class ConvBNFn : public torch::autograd::Function<ConvBNFn> {
     ConvSaved sv;
     Tensor y = conv_forward(c, sv);
     EdgeMap em;
-    edge_map_conv(em, c);
-    ctx->saved_data["edges"] = em.e;
-    sv.to_ctx(ctx, "");
-    ctx->save_for_backward(sv.t);
+    save_edges(ctx, em, walk_conv(em, c));
+    sv.save(ctx);
     return y;
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    ConvSaved sv = ConvSaved::from_ctx(ctx, "", ctx->get_saved_variables(), 0);
-    const int64_t K = sv.dims[5];
-    const int64_t n_fac = (int64_t)sv.t.size() - (int64_t)kSavedFixed - K;
-    variable_list out(conv_positions(K, n_fac));
-    put_grads(out, 0, K, conv_backward(sv, grads[0], conv_needs(ctx, K, 0)));
-    return out;
+    return conv_backward(ConvSaved::load(ctx), grads[0], Edges<ConvPos>(ctx));
   }
 };
 
@@ -1022,34 +1020,45 @@ class ConvBNFn : public torch::autograd::Function<ConvBNFn> {
 // ---------------------------------------------------------------------------
 class BNActFn : public torch::autograd::Function<BNActFn> {
  public:
+  struct Pos {
+    int64_t x, w, b;
+  };
+  struct Saved {
+    Tensor x, y, w, mean, invstd, b, valid;  // y: only with the ReLU
+    std::vector<Tensor*> slots() { return {&x, &y, &w, &mean, &invstd, &b, &valid}; }
+  };
   static Tensor forward(AutogradContext* ctx, Tensor x, OptT w, OptT b, OptT rm, OptT rv,
                         OptT nbt, double momentum, double eps, bool relu, OptT valid) {
     req(x, "x");
-    Tensor xc = rows2d(x);
-    Tensor mean, invstd;
-    BnState st{w, b, rm, rv, nbt, momentum, eps, valid};
-    Tensor y = bn_forward(xc, st, relu, mean, invstd);
-    ctx->saved_data["relu"] = relu;
+    Saved sv;
+    sv.x = rows2d(x);
+    Tensor y = bn_forward(sv.x, BnState{w, b, rm, rv, nbt, momentum, eps, valid}, relu, sv.mean,
+                          sv.invstd);
     EdgeMap em;
-    em.tensor();
-    em.opt(w);
-    em.opt(b);
+    const Pos pos{em.tensor(), em.opt(w), em.opt(b)};  // braces evaluate left to right
     em.opt(rm);
     em.opt(rv);
     em.opt(nbt);
-    ctx->saved_data["edges"] = em.e;
-    ctx->save_for_backward({xc, relu ? y : Tensor(), has(w) ? *w : Tensor(), mean, invstd,
-                            has(b) ? *b : Tensor(), has(valid) ? *valid : Tensor()});
+    em.other(3);  // momentum, eps, relu
+    em.opt(valid);
+    save_edges(ctx, em, pos);
+    if (relu) sv.y = y;
+    sv.w = opt_or_undef(w);
+    sv.b = opt_or_undef(b);
+    sv.valid = opt_or_undef(valid);
+    save_slots(ctx, sv);
     return y;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto sv = ctx->get_saved_variables();
-    Tensor dw, db;
-    OptT y = sv[1].defined() ? OptT(sv[1]) : OptT();
-    OptT w = sv[2].defined() ? OptT(sv[2]) : OptT();
-    Tensor dx = bn_backward(sv[0], y, grads[0], w, sv[3], sv[4], need(ctx, 1), need(ctx, 2), dw,
-                           db, nullptr, &sv[5], sv[6]);
-    return {dx, dw, db, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    Saved sv;
+    load_slots(ctx, sv);
+    const Edges<Pos> ed(ctx);
+    const Pos& pos = ed.pos;
+    variable_list out = ed.grads();
+    out[pos.x] = bn_backward(sv.x, undef_to_opt(sv.y), grads[0], undef_to_opt(sv.w), sv.mean,
+                             sv.invstd, ed.need(pos.w), ed.need(pos.b), out[pos.w], out[pos.b],
+                             nullptr, &sv.b, sv.valid);
+    return out;
   }
 };
 
@@ -1127,115 +1136,91 @@ void linear_backward(const Tensor& Gin, const std::vector<Tensor>& As, const Ten
   }
   dW = Tensor();
   db = Tensor();
-  bool any_a = false;
-  for (int i = 0; i < nb; ++i) any_a = any_a || need_a[i];
-  std::vector<const float*> wAp;  // weight gradient deferred into the data gradient's launch
-  std::vector<int64_t> wlda, wlddw;
-  std::vector<float*> wdWp;
-  float* wdb = nullptr;
-  Tensor wkeep, wkeep_b;  // the gradient buffers stay allocated until the launch
+  GradW gw;
   if (need_w || need_b) {
-    Tensor gw = need_w ? grad_like(W) : at::empty_like(W, at::MemoryFormat::Contiguous);
-    Tensor gb = need_b ? ((b_param && b_param->defined()) ? grad_like(*b_param)
-                                                          : at::empty({N}, W.options()))
-                       : Tensor();
-    if (M > 0) {
-      std::vector<const float*> Ap(nb);
-      std::vector<int64_t> lda(nb), lddw(nb, W.size(1));
-      std::vector<float*> dWp(nb);
-      for (int i = 0; i < nb; ++i) {
-        Ap[i] = As[i].data_ptr<float>();
-        lda[i] = ld_of(As[i]);
-        dWp[i] = gw.data_ptr<float>() + offs[i];
-      }
-      if (any_a && fused_bwd_flag()) {
-        wAp = Ap;
-        wlda = lda;
-        wlddw = lddw;
-        wdWp = dWp;
-        wdb = need_b ? gb.data_ptr<float>() : nullptr;
-        wkeep = gw;
-        wkeep_b = gb;
-      } else {  // weight only: the one-launch path with no data items
-        std::vector<const float*> noW;
-        std::vector<int64_t> noL;
-        std::vector<float*> noD;
-        proj_bwd_both(G, Ap, lda, kb, dWp, lddw, need_b ? gb.data_ptr<float>() : nullptr, noW,
-                      noL, noL, noD, noL, s, 0, false);
-      }
-    } else {
-      gw.zero_();
-      if (need_b) gb.zero_();
+    Tensor w = need_w ? grad_like(W) : at::empty_like(W, at::MemoryFormat::Contiguous);
+    gw.out.push_back(w);
+    if (need_b) {
+      db = (b_param && b_param->defined()) ? grad_like(*b_param) : at::empty({N}, W.options());
+      gw.db = db.data_ptr<float>();
+      gw.out.push_back(db);
     }
-    if (need_w) dW = gw;
-    if (need_b) db = gb;
+    gw.kb = kb;
+    gw.lddw.assign(nb, W.size(1));
+    for (int i = 0; i < nb; ++i) {
+      gw.A.push_back(As[i].data_ptr<float>());
+      gw.lda.push_back(ld_of(As[i]));
+      gw.dW.push_back(w.data_ptr<float>() + offs[i]);
+    }
+    if (need_w) dW = w;
   }
   dAs.assign(nb, Tensor());
   std::vector<int> idx;
   for (int i = 0; i < nb; ++i)
     if (need_a[i]) idx.push_back(i);
-  if (!idx.empty()) {
-    std::vector<const float*> Wp;
-    std::vector<int64_t> ldw, kbs, ldda;
-    std::vector<float*> dA;
-    // accumulate into the given destinations only when every block has one
-    bool into = dA_into != nullptr;
-    for (int i : idx)
-      into = into && (int)dA_into->size() > i && (*dA_into)[i].defined() &&
-             (*dA_into)[i].size(0) == M && (*dA_into)[i].size(1) == kb[i] &&
-             (*dA_into)[i].stride(1) == 1;
-    for (int i : idx) {
-      dAs[i] = into ? (*dA_into)[i] : at::empty({M, kb[i]}, W.options());
-      Wp.push_back(W.data_ptr<float>() + offs[i]);
-      ldw.push_back(W.stride(0));
-      kbs.push_back(kb[i]);
-      dA.push_back(dAs[i].data_ptr<float>());
-      ldda.push_back(into ? dAs[i].stride(0) : kb[i]);
-    }
-    if (M > 0) {
-      const int acc = into ? into_acc : 0;
-      if (!wAp.empty())
-        proj_bwd_both(G, wAp, wlda, kb, wdWp, wlddw, wdb, Wp, ldw, kbs, dA, ldda, s, acc,
-                      force_defer);
-      else
-        proj_bwd_data(G, Wp, ldw, kbs, dA, ldda, s, acc);
-    }
+  GradD gd;
+  // accumulate into the given destinations only when every block has one
+  bool into = dA_into != nullptr;
+  for (int i : idx)
+    into = into && (int)dA_into->size() > i && (*dA_into)[i].defined() &&
+           (*dA_into)[i].size(0) == M && (*dA_into)[i].size(1) == kb[i] &&
+           (*dA_into)[i].stride(1) == 1;
+  for (int i : idx) {
+    dAs[i] = into ? (*dA_into)[i] : at::empty({M, kb[i]}, W.options());
+    gd.W.push_back(W.data_ptr<float>() + offs[i]);
+    gd.ldw.push_back(W.stride(0));
+    gd.kb.push_back(kb[i]);
+    gd.dA.push_back(dAs[i].data_ptr<float>());
+    gd.ldda.push_back(into ? dAs[i].stride(0) : kb[i]);
   }
+  gd.acc = into ? into_acc : 0;
+  linear_grads(G, (need_w || need_b) ? &gw : nullptr, idx.empty() ? nullptr : &gd, s,
+               force_defer);
+}
+
+// the input blocks of a node: checked, unit inner stride
+std::vector<Tensor> input_blocks(at::TensorList in) {
+  std::vector<Tensor> blocks;
+  for (const auto& a : in) {
+    req(a, "input");
+    blocks.push_back(rows2d(a));
+  }
+  return blocks;
 }
 
 class LinearFn : public torch::autograd::Function<LinearFn> {
  public:
+  struct Pos {
+    int64_t W, b, As0;  // As[i] is at As0 + i
+  };
+  struct Saved {
+    Tensor W, b;
+    std::vector<Tensor> As;  // the tail
+    std::vector<Tensor*> slots() { return {&W, &b}; }
+  };
   static Tensor forward(AutogradContext* ctx, Tensor W, OptT b, at::TensorList As_in) {
     req(W, "weight");
-    std::vector<Tensor> As;
-    for (const auto& a : As_in) {
-      req(a, "input");
-      As.push_back(rows2d(a));
-    }
-    Tensor Wc = W.stride(1) == 1 ? W : W.contiguous();
-    Tensor out = linear_forward(As, Wc, b);
-    ctx->saved_data["has_b"] = has(b);
+    Saved sv;
+    sv.As = input_blocks(As_in);
+    sv.W = row_major(W);
+    sv.b = opt_or_undef(b);
+    Tensor out = linear_forward(sv.As, sv.W, b);
     EdgeMap em;
-    em.tensor();
-    em.opt(b);
-    em.list(As_in);
-    ctx->saved_data["edges"] = em.e;
-    std::vector<Tensor> save = {Wc, has(b) ? *b : Tensor()};
-    save.insert(save.end(), As.begin(), As.end());
-    ctx->save_for_backward(save);
+    const Pos pos{em.tensor(), em.opt(b), em.list(As_in)};  // braces evaluate left to right
+    save_edges(ctx, em, pos);
+    save_slots(ctx, sv, sv.As);
     return out;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto sv = ctx->get_saved_variables();
-    Tensor W = sv[0], b = sv[1];
-    std::vector<Tensor> As(sv.begin() + 2, sv.end());
-    std::vector<bool> need_a(As.size());
-    for (size_t i = 0; i < As.size(); ++i) need_a[i] = need(ctx, 2 + (int64_t)i);
-    Tensor dW, db;
+    Saved sv;
+    sv.As = load_slots(ctx, sv);
+    const Edges<Pos> ed(ctx);
+    const Pos& pos = ed.pos;
+    variable_list out = ed.grads();
     std::vector<Tensor> dAs;
-    linear_backward(grads[0], As, W, need(ctx, 0), need(ctx, 1), need_a, dW, db, dAs, &b);
-    variable_list out = {dW, db};
-    out.insert(out.end(), dAs.begin(), dAs.end());
+    linear_backward(grads[0], sv.As, sv.W, ed.need(pos.W), ed.need(pos.b),
+                    ed.need(pos.As0, sv.As.size()), out[pos.W], out[pos.b], dAs, &sv.b);
+    std::copy(dAs.begin(), dAs.end(), out.begin() + pos.As0);
     return out;
   }
 };
@@ -1266,92 +1251,131 @@ std::vector<Tensor> take_tap() {
 // Linear(blocks) -> BN -> ReLU -> Linear -> BN -> ReLU (NodeEdgeInt WV_*, two
 // layers of a readout MLP)
 // ---------------------------------------------------------------------------
+// The parameters of one such MLP: the 14 tensors in the order the Python side
+// lists them (hlhgat.ops._mlp2_params) and the BatchNorm hyper-parameters.
+struct MlpParams {
+  Tensor W0;
+  OptT b0, g1, be1, rm1, rv1, nbt1;
+  Tensor W3;
+  OptT b3, g4, be4, rm4, rv4, nbt4;
+  double mom1, eps1, mom4, eps4;
+  static MlpParams of_list(at::TensorList p, double mom1, double eps1, double mom4, double eps4) {
+    TORCH_INTERNAL_ASSERT(p.size() == 14);
+    auto it = p.begin();
+    auto t = [&it]() -> const Tensor& { return *it++; };  // braces evaluate left to right
+    return MlpParams{t(), t(), t(), t(), t(), t(), t(), t(), t(), t(), t(), t(), t(), t(),
+                     mom1, eps1, mom4, eps4};
+  }
+  BnState bn1(const OptT& valid = OptT()) const {
+    return BnState{g1, be1, rm1, rv1, nbt1, mom1, eps1, valid};
+  }
+  BnState bn4(const OptT& valid = OptT()) const {
+    return BnState{g4, be4, rm4, rv4, nbt4, mom4, eps4, valid};
+  }
+};
+// The positions of the eight trainable ones, from the walk of the 14: separate
+// arguments (an absent optional is no edge) or the elements of one list
+// argument (every element is an edge).
+struct MlpPos {
+  int64_t W0, b0, g1, be1, W3, b3, g4, be4;
+};
+MlpPos walk_mlp(EdgeMap& em, const MlpParams& p, bool in_list) {
+  auto o = [&](const OptT& t) { return in_list ? em.tensor() : em.opt(t); };
+  MlpPos q;
+  q.W0 = em.tensor();
+  q.b0 = o(p.b0);
+  q.g1 = o(p.g1);
+  q.be1 = o(p.be1);
+  o(p.rm1);
+  o(p.rv1);
+  o(p.nbt1);
+  q.W3 = em.tensor();
+  q.b3 = o(p.b3);
+  q.g4 = o(p.g4);
+  q.be4 = o(p.be4);
+  o(p.rm4);
+  o(p.rv4);
+  o(p.nbt4);
+  return q;
+}
+
+// What the forward keeps of one MLP: its activations and batch statistics,
+// and the parameters its backward reads (the biases as gradient bucket targets).
+struct MlpSaved {
+  Tensor h1, a1, m1, i1, h2, y, m4, i4;
+  Tensor W0, b0, g1, be1, W3, b3, g4, be4;
+  std::vector<Tensor*> slots() {
+    return {&h1, &a1, &m1, &i1, &h2, &y, &m4, &i4, &W0, &b0, &g1, &be1, &W3, &b3, &g4, &be4};
+  }
+  void params(const MlpParams& p, const Tensor& W0_kept, const Tensor& W3_kept) {
+    W0 = W0_kept;
+    b0 = opt_or_undef(p.b0);
+    g1 = opt_or_undef(p.g1);
+    be1 = opt_or_undef(p.be1);
+    W3 = W3_kept;
+    b3 = opt_or_undef(p.b3);
+    g4 = opt_or_undef(p.g4);
+    be4 = opt_or_undef(p.be4);
+  }
+};
+
+// Backward of BN1 -> ReLU -> Linear3 -> BN4 -> ReLU given gy = dL/dy: returns
+// dL/dh1 (written into dx_into when given) and puts the six parameter
+// gradients of those layers at their positions in `out`.  valid: the
+// static-shape row count (undefined: all rows).
+template <class P>
+Tensor mlp2_backward_tail(const MlpSaved& s, const Tensor& gy, const Edges<P>& ed,
+                          const MlpPos& pos, variable_list& out, const Tensor& valid = Tensor(),
+                          const Tensor* dx_into = nullptr) {
+  // an output nobody used (NodeEdgeInt has two): a zero gradient
+  Tensor gyc = gy.defined() ? gy : at::zeros_like(s.y);
+  Tensor dh2 = bn_backward(s.h2, OptT(s.y), gyc, undef_to_opt(s.g4), s.m4, s.i4, ed.need(pos.g4),
+                           ed.need(pos.be4), out[pos.g4], out[pos.be4], nullptr, &s.be4, valid);
+  std::vector<Tensor> da1;
+  linear_backward(dh2, {s.a1}, s.W3, ed.need(pos.W3), ed.need(pos.b3), {true}, out[pos.W3],
+                  out[pos.b3], da1, &s.b3);
+  return bn_backward(s.h1, OptT(s.a1), da1[0], undef_to_opt(s.g1), s.m1, s.i1, ed.need(pos.g1),
+                     ed.need(pos.be1), out[pos.g1], out[pos.be1], dx_into, &s.be1, valid);
+}
+
 class MLP2Fn : public torch::autograd::Function<MLP2Fn> {
  public:
+  struct Pos {
+    int64_t blocks0;  // blocks[i] is at blocks0 + i
+    MlpPos mlp;
+  };
   static Tensor forward(AutogradContext* ctx, at::TensorList blocks_in, Tensor W0, OptT b0,
                         OptT g1, OptT be1, OptT rm1, OptT rv1, OptT nbt1, Tensor W3, OptT b3,
                         OptT g4, OptT be4, OptT rm4, OptT rv4, OptT nbt4, double mom1, double eps1,
                         double mom4, double eps4) {
-    std::vector<Tensor> blocks;
-    for (const auto& a : blocks_in) {
-      req(a, "input");
-      blocks.push_back(rows2d(a));
-    }
-    Tensor W0c = W0.stride(1) == 1 ? W0 : W0.contiguous();
-    Tensor W3c = W3.stride(1) == 1 ? W3 : W3.contiguous();
-    Tensor h1, h2, m1, i1, m4, i4;
-    Tensor a1 = linear_bn_forward(blocks, W0c, b0, BnState{g1, be1, rm1, rv1, nbt1, mom1, eps1},
-                                  true, h1, m1, i1);
-    Tensor y = linear_bn_forward({a1}, W3c, b3, BnState{g4, be4, rm4, rv4, nbt4, mom4, eps4},
-                                 true, h2, m4, i4);
-    if (tap_state().on) tap_state().taken.push_back(a1.clone());  // the hidden ReLU
-    ctx->saved_data["nb"] = (int64_t)blocks.size();
-    {
-      EdgeMap em;
-      em.list(blocks_in);
-      em.tensor();  // W0
-      em.opt(b0);
-      em.opt(g1);
-      em.opt(be1);
-      em.opt(rm1);
-      em.opt(rv1);
-      em.opt(nbt1);
-      em.tensor();  // W3
-      em.opt(b3);
-      em.opt(g4);
-      em.opt(be4);
-      em.opt(rm4);
-      em.opt(rv4);
-      em.opt(nbt4);
-      for (int i = 0; i < 4; ++i) em.other();
-      ctx->saved_data["edges"] = em.e;
-    }
-    ctx->saved_data["has_b0"] = has(b0);
-    ctx->saved_data["has_b3"] = has(b3);
-    std::vector<Tensor> save = {W0c, h1, a1, m1, i1, has(g1) ? *g1 : Tensor(), W3c, h2, y, m4, i4,
-                                has(g4) ? *g4 : Tensor(), has(b0) ? *b0 : Tensor(),
-                                has(be1) ? *be1 : Tensor(), has(b3) ? *b3 : Tensor(),
-                                has(be4) ? *be4 : Tensor()};
-    save.insert(save.end(), blocks.begin(), blocks.end());
-    ctx->save_for_backward(save);
-    return y;
+    const MlpParams p{W0, b0,  g1,  be1, rm1,  rv1,  nbt1, W3,   b3,
+                      g4, be4, rm4, rv4, nbt4, mom1, eps1, mom4, eps4};
+    const std::vector<Tensor> blocks = input_blocks(blocks_in);
+    MlpSaved m;
+    const Tensor W0c = row_major(W0), W3c = row_major(W3);
+    m.params(p, W0c, W3c);
+    m.a1 = linear_bn_forward(blocks, m.W0, b0, p.bn1(), true, m.h1, m.m1, m.i1);
+    m.y = linear_bn_forward({m.a1}, m.W3, b3, p.bn4(), true, m.h2, m.m4, m.i4);
+    if (tap_state().on) tap_state().taken.push_back(m.a1.clone());  // the hidden ReLU
+    EdgeMap em;
+    const Pos pos{em.list(blocks_in), walk_mlp(em, p, false)};  // braces: left to right
+    em.other(4);  // mom1, eps1, mom4, eps4
+    save_edges(ctx, em, pos);
+    save_slots(ctx, m, blocks);
+    return m.y;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto sv = ctx->get_saved_variables();
-    const int64_t nb = ctx->saved_data["nb"].toInt();
-    Tensor W0 = sv[0], h1 = sv[1], a1 = sv[2], m1 = sv[3], i1 = sv[4], g1 = sv[5], W3 = sv[6],
-           h2 = sv[7], y = sv[8], m4 = sv[9], i4 = sv[10], g4 = sv[11];
-    Tensor b0 = sv[12], be1 = sv[13], b3 = sv[14], be4 = sv[15];
-    std::vector<Tensor> blocks(sv.begin() + 16, sv.end());
-    // positions: blocks[0..nb), W0, b0, g1, be1, rm1, rv1, nbt1, W3, b3, g4, be4, rm4, rv4,
-    //            nbt4, mom1, eps1, mom4, eps4
-    const int64_t P = nb;
-    variable_list out(nb + 18);
-    Tensor dg4, dbe4, dg1, dbe1;
-    Tensor dh2 = bn_backward(h2, OptT(y), grads[0], g4.defined() ? OptT(g4) : OptT(), m4, i4,
-                             need(ctx, P + 9), need(ctx, P + 10), dg4,
-                             dbe4, nullptr, &be4);
-    out[P + 9] = dg4;
-    out[P + 10] = dbe4;
-    Tensor dW3, db3, dW0, db0;
-    std::vector<Tensor> da1;
-    linear_backward(dh2, {a1}, W3, need(ctx, P + 7), need(ctx, P + 8), {true},
-                    dW3, db3, da1, &b3);
-    out[P + 7] = dW3;
-    out[P + 8] = db3;
-    Tensor dh1 = bn_backward(h1, OptT(a1), da1[0], g1.defined() ? OptT(g1) : OptT(), m1, i1,
-                             need(ctx, P + 2), need(ctx, P + 3), dg1,
-                             dbe1, nullptr, &be1);
-    out[P + 2] = dg1;
-    out[P + 3] = dbe1;
-    std::vector<bool> need_a(nb);
-    for (int64_t i = 0; i < nb; ++i) need_a[i] = need(ctx, i);
+    MlpSaved m;
+    const std::vector<Tensor> blocks = load_slots(ctx, m);
+    const Edges<Pos> ed(ctx);
+    const Pos& pos = ed.pos;
+    variable_list out = ed.grads();
+    Tensor dh1 = mlp2_backward_tail(m, grads[0], ed, pos.mlp, out);
     std::vector<Tensor> dblocks;
-    linear_backward(dh1, blocks, W0, need(ctx, P), need(ctx, P + 1), need_a,
-                    dW0, db0, dblocks, &b0);
-    out[P] = dW0;
-    out[P + 1] = db0;
-    for (int64_t i = 0; i < nb; ++i) out[i] = dblocks[i];
+    linear_backward(dh1, blocks, m.W0, ed.need(pos.mlp.W0), ed.need(pos.mlp.b0),
+                    ed.need(pos.blocks0, blocks.size()), out[pos.mlp.W0], out[pos.mlp.b0],
+                    dblocks, &m.b0);
+    std::copy(dblocks.begin(), dblocks.end(), out.begin() + pos.blocks0);
     return out;
   }
 };
@@ -1493,10 +1517,6 @@ int64_t fork_side_stream(int64_t device) {
   return reinterpret_cast<int64_t>(Fork::side_of((int)device).stream());
 }
 
-struct SideMlp {  // [W0, b0, g1, be1, rm1, rv1, nbt1, W3, b3, g4, be4, rm4, rv4, nbt4]
-  Tensor h1, a1, m1, i1, h2, y, m4, i4;
-};
-
 // Wt = [Wn_b; We_a], Ws = [We_b; Wn_a], bt = [b_n; 0], bs = [b_e; 0]
 // (W0 = [W_a | W_b], lib/Hodge_Cheb_Conv.py:307-308) into one flat tensor
 // [Wt | Ws | bt | bs]: both sides' first Linear on x_t (x_s) is ONE GEMM.
@@ -1516,6 +1536,13 @@ void pack_nei(CopyBlocks& cb, const Tensor& Wn, const Tensor& bn0, const Tensor&
   cb.add(nullptr, 0, bs + de, dn, 1, dn);
 }
 
+// the pack's size and its four views, P = dn + de
+inline int64_t nei_pack_floats(int64_t P, int64_t d) { return 2 * P * d + 2 * P; }
+std::tuple<Tensor, Tensor, Tensor, Tensor> nei_pack_views(const Tensor& pk, int64_t P, int64_t d) {
+  return {pk.narrow(0, 0, P * d).view({P, d}), pk.narrow(0, P * d, P * d).view({P, d}),
+          pk.narrow(0, 2 * P * d, P), pk.narrow(0, 2 * P * d + P, P)};  // Wt, Ws, bt, bs
+}
+
 // Every NodeEdgeInt's pack of one forward in one launch (hlhgat.ops.nei_prepack):
 // groups[i] = {W0n, b0n, W0e, b0e}.
 std::vector<Tensor> nei_prepack(std::vector<std::vector<Tensor>> groups) {
@@ -1524,13 +1551,12 @@ std::vector<Tensor> nei_prepack(std::vector<std::vector<Tensor>> groups) {
   void* s = nullptr;  // the current stream (nullptr is the legacy default stream)
   for (auto& g : groups) {
     TORCH_CHECK(g.size() == 4, "hlhgat: nei_prepack: {W0n, b0n, W0e, b0e} per module");
-    Tensor Wn = g[0].stride(1) == 1 ? g[0] : g[0].contiguous();
-    Tensor We = g[2].stride(1) == 1 ? g[2] : g[2].contiguous();
+    Tensor Wn = row_major(g[0]), We = row_major(g[2]);
     Tensor bn0 = g[1].contiguous(), be0 = g[3].contiguous();
     req(Wn, "W0n");
     const int64_t d = Wn.size(1) / 2, dn = Wn.size(0), de = We.size(0);
     TORCH_CHECK(We.size(1) == 2 * d, "hlhgat: nei_prepack: W0n / W0e widths differ");
-    Tensor pk = at::empty({2 * (dn + de) * d + 2 * (dn + de)}, Wn.options());
+    Tensor pk = at::empty({nei_pack_floats(dn + de, d)}, Wn.options());
     if (cb.src.size() + 8 > (size_t)HLHGAT_MAX_COPY_BLOCKS) {
       cb.run(stream_of(Wn));
       cb = CopyBlocks();
@@ -1578,6 +1604,21 @@ void set_chain_bwd(bool on) { chain_bwd_flag() = on; }
 
 class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
  public:
+  struct Pos {
+    int64_t x_t, x_s;
+    MlpPos n, e;  // WV_Node / WV_Edge
+  };
+  struct Saved {
+    Tensor xt, xs, rowptr, eids, ei, rD, Wt, Ws;
+    Tensor valid_t, valid_s;  // valid-row counts
+    MlpSaved n, e;            // WV_Node / WV_Edge; their W0, b0: gradient bucket targets
+    std::vector<Tensor*> slots() {
+      std::vector<Tensor*> v{&xt, &xs, &rowptr, &eids, &ei, &rD, &Wt, &Ws, &valid_t, &valid_s};
+      for (MlpSaved* m : {&n, &e})
+        for (Tensor* t : m->slots()) v.push_back(t);
+      return v;
+    }
+  };
   static variable_list forward(AutogradContext* ctx, Tensor x_t, Tensor x_s, Tensor rowptr,
                                Tensor eids, Tensor ei, Tensor rD, at::TensorList pn,
                                at::TensorList pe, double mom1n, double eps1n, double mom4n,
@@ -1592,33 +1633,27 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
     TORCH_CHECK(xs.size(1) == d, "hlhgat: NodeEdgeInt x_t / x_s widths differ");
     TORCH_CHECK(ei.size(1) == E, "hlhgat: x_s rows != |B1| edges");
     TORCH_CHECK(rD.numel() == N, "hlhgat: D has ", rD.numel(), " entries, x_t has ", N, " rows");
-    const Tensor &W0n = pn[0], &W0e = pe[0];
-    TORCH_CHECK(W0n.size(1) == 2 * d && W0e.size(1) == 2 * d, "hlhgat: WV first Linear expects ",
-                2 * d, " input features");
-    const int64_t dn = W0n.size(0), de = W0e.size(0);
+    const MlpParams mn = MlpParams::of_list(pn, mom1n, eps1n, mom4n, eps4n);
+    const MlpParams me = MlpParams::of_list(pe, mom1e, eps1e, mom4e, eps4e);
+    TORCH_CHECK(mn.W0.size(1) == 2 * d && me.W0.size(1) == 2 * d,
+                "hlhgat: WV first Linear expects ", 2 * d, " input features");
+    const int64_t dn = mn.W0.size(0), de = me.W0.size(0);
     // Wt = [Wn_b; We_a], Ws = [We_b; Wn_a], bt = [b_n; 0], bs = [b_e; 0]: one launch
-    Tensor Wn = W0n.stride(1) == 1 ? W0n : W0n.contiguous();
-    Tensor We = W0e.stride(1) == 1 ? W0e : W0e.contiguous();
-    Tensor bn0 = pn[1].contiguous(), be0 = pe[1].contiguous();
+    Tensor Wn = row_major(mn.W0), We = row_major(me.W0);
+    Tensor bn0 = mn.b0->contiguous(), be0 = me.b0->contiguous();
     const int64_t P = dn + de;
-    Tensor Wt, Ws, bt, bs;
+    Tensor pk;
     if (has(packed)) {  // built for the whole forward by nei_prepack
-      TORCH_CHECK(packed->numel() == 2 * P * d + 2 * P && packed->is_contiguous(),
+      TORCH_CHECK(packed->numel() == nei_pack_floats(P, d) && packed->is_contiguous(),
                   "hlhgat: nei_value: packed weights have the wrong size");
-      Wt = packed->narrow(0, 0, P * d).view({P, d});
-      Ws = packed->narrow(0, P * d, P * d).view({P, d});
-      bt = packed->narrow(0, 2 * P * d, P);
-      bs = packed->narrow(0, 2 * P * d + P, P);
+      pk = *packed;
     } else {
-      Tensor pk = at::empty({2 * P * d + 2 * P}, xt.options());
+      pk = at::empty({nei_pack_floats(P, d)}, xt.options());
       CopyBlocks cb;
       pack_nei(cb, Wn, bn0, We, be0, d, dn, de, pk);
       cb.run(stream_of(xt));
-      Wt = pk.narrow(0, 0, P * d).view({P, d});
-      Ws = pk.narrow(0, P * d, P * d).view({P, d});
-      bt = pk.narrow(0, 2 * P * d, P);
-      bs = pk.narrow(0, 2 * P * d + P, P);
     }
+    const auto [Wt, Ws, bt, bs] = nei_pack_views(pk, P, d);
     Fork fk(xt.get_device());
     const bool chain = chain_flag();
     // the edge GEMM needs this node's own weight pack (built on the main
@@ -1649,10 +1684,10 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
       int64_t ldz;
       float ca, cb;
     };
-    auto side = [&](const at::TensorList& p, const Tensor& h1, double m1, double e1, double m4,
-                    double e4, const OptT& valid, SideMlp& o, const Producer* pr) {
+    auto side = [&](const MlpParams& p, const Tensor& h1, const OptT& valid, MlpSaved& o,
+                    const Producer* pr) {
       o.h1 = h1;
-      const BnState bst{p[2], p[3], p[4], p[5], p[6], m1, e1, valid};
+      o.params(p, p.W0, p.W3);
       if (pr) {
         const int64_t n = h1.size(0), C = h1.size(1);
         if (pr->edge)
@@ -1667,18 +1702,17 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
                                     ld_of(h1), stream_of(h1)),
               "incidence_step");
       }
-      o.a1 = bn_forward(h1, bst, true, o.m1, o.i1);
-      Tensor W3 = p[7].stride(1) == 1 ? p[7] : p[7].contiguous();
-      o.y = linear_bn_forward({o.a1}, W3, p[8],
-                              BnState{p[9], p[10], p[11], p[12], p[13], m4, e4, valid}, true,
-                              o.h2, o.m4, o.i4);
+      o.a1 = bn_forward(h1, p.bn1(valid), true, o.m1, o.i1);
+      o.y = linear_bn_forward({o.a1}, row_major(p.W3), p.b3, p.bn4(valid), true, o.h2, o.m4,
+                              o.i4);
     };
     auto lin_into = [](const Tensor& A, const Tensor& W, const Tensor& b, Tensor& out) {
       if (A.size(0) > 0)
         proj_fwd({A.data_ptr<float>()}, {ld_of(A)}, {W.data_ptr<float>()}, {W.stride(0)},
                  {A.size(1)}, A.size(0), W.size(0), b.data_ptr<float>(), out, stream_of(A));
     };
-    SideMlp tn, te;
+    Saved sv{xt, xs, rowptr, eids, ei, rD, Wt, Ws, opt_or_undef(valid_t), opt_or_undef(valid_s)};
+    MlpSaved &tn = sv.n, &te = sv.e;
     // Yt is read on the side stream after the exchange (no join at the end in
     // chain mode): keep its block for the side stream
     if (chain) Yt.record_stream(fk.side);
@@ -1693,12 +1727,12 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
       TStreamGuard g(fk.side);
       const Producer pr{true, Yt.data_ptr<float>() + dn, dn + de,
                         Ys.data_ptr<float>(), de + dn, 0.5f, 0.5f};
-      side(pe, h1s, mom1e, eps1e, mom4e, eps4e, valid_s, te, E > 0 ? &pr : nullptr);
+      side(me, h1s, valid_s, te, E > 0 ? &pr : nullptr);
     }
     {  // node side: h1_t = Qt + rD * |B1| P1, then its MLP
       const Producer pr{false, Ys.data_ptr<float>() + de, de + dn,
                         Yt.data_ptr<float>(), dn + de, 1.f, 1.f};
-      side(pn, h1t, mom1n, eps1n, mom4n, eps4n, valid_t, tn, N > 0 ? &pr : nullptr);
+      side(mn, h1t, valid_t, tn, N > 0 ? &pr : nullptr);
     }
     if (!chain || tap_state().on) fk.main_waits_side();
     if (tap_state().on) {
@@ -1708,29 +1742,24 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
     fk.escape({te.a1, te.m1, te.i1, te.h2, te.y, te.m4, te.i4});
     {
       EdgeMap em;
-      for (int i = 0; i < 6; ++i) em.tensor();
-      em.list(pn);
-      em.list(pe);
-      for (int i = 0; i < 8; ++i) em.other();
+      Pos pos;
+      pos.x_t = em.tensor();
+      pos.x_s = em.tensor();
+      em.tensor(4);  // rowptr, eids, ei, rD
+      pos.n = walk_mlp(em, mn, true);
+      pos.e = walk_mlp(em, me, true);
+      em.other(8);  // mom1n .. eps4e
       em.opt(valid_t);
       em.opt(valid_s);
       em.opt(gsink_t);
       em.opt(gsink_s);
       em.opt(gflag_t);
       em.opt(gflag_s);
-      em.opt(packed);
-      ctx->saved_data["edges"] = em.e;
+      em.opt(packed);  // no gradient: the weights' gradients go to pn / pe
+      save_edges(ctx, em, pos);
     }
-    ctx->saved_data["dims"] = std::vector<int64_t>{N, E, d, dn, de};
     if (chain && chain_bwd_flag()) ctx->saved_data["chain"] = true;
-    ctx->save_for_backward({xt, xs, rowptr, eids, ei, rD, Wt, Ws, pn[2], pn[7], pn[9], pe[2],
-                            pe[7], pe[9], tn.h1, tn.a1, tn.m1, tn.i1, tn.h2, tn.y, tn.m4, tn.i4,
-                            te.h1, te.a1, te.m1, te.i1, te.h2, te.y, te.m4, te.i4,
-                            // 30..: W0, b0, be1, b3, be4 per side (gradient bucket targets)
-                            pn[0], pn[1], pn[3], pn[8], pn[10], pe[0], pe[1], pe[3], pe[8],
-                            pe[10],
-                            // 40, 41: valid-row counts of the node / edge sides
-                            has(valid_t) ? *valid_t : Tensor(), has(valid_s) ? *valid_s : Tensor()});
+    save_slots(ctx, sv);
     // gradient sinks of x_t / x_s (DenseConcat slab views): kept outside the
     // saved variables -- other views' backwards add into the same slab in
     // place before this node's backward runs, which is the point
@@ -1748,43 +1777,23 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto sv = ctx->get_saved_variables();
-    const auto dims = ctx->saved_data["dims"].toIntVector();
-    const int64_t N = dims[0], E = dims[1], d = dims[2], dn = dims[3], de = dims[4];
-    Tensor xt = sv[0], xs = sv[1], rowptr = sv[2], eids = sv[3], ei = sv[4], rD = sv[5],
-           Wt = sv[6], Ws = sv[7];
-    // positions: x_t 0, x_s 1, rowptr 2, eids 3, ei 4, rD 5, pn 6..19, pe 20..33, hyper 34..41,
-    //            valid_t 42, valid_s 43, gsink_t 44, gsink_s 45, gflag_t 46, gflag_s 47,
-    //            packed 48 (no gradient: the weights' gradients go to pn / pe)
-    variable_list out(49);
-    const int64_t PN = 6, PE = 20;
-    auto side_bwd = [&](const Tensor& gy, int64_t P, const Tensor& g1, const Tensor& W3,
-                        const Tensor& g4, int o0, Tensor dest, int q0, const Tensor& valid) {
-      const Tensor &be1 = sv[q0 + 2], &b3 = sv[q0 + 3], &be4 = sv[q0 + 4];
-      Tensor h1 = sv[o0], a1 = sv[o0 + 1], m1 = sv[o0 + 2], i1 = sv[o0 + 3], h2 = sv[o0 + 4],
-             y = sv[o0 + 5], m4 = sv[o0 + 6], i4 = sv[o0 + 7];
-      Tensor dg4, dbe4, dg1, dbe1, dW3, db3;
-      Tensor gyc = gy.defined() ? gy : at::zeros_like(y);
-      Tensor dh2 = bn_backward(h2, OptT(y), gyc, OptT(g4), m4, i4, need(ctx, P + 9),
-                               need(ctx, P + 10), dg4, dbe4, nullptr, &be4, valid);
-      std::vector<Tensor> da1;
-      linear_backward(dh2, {a1}, W3, need(ctx, P + 7), need(ctx, P + 8), {true}, dW3, db3, da1,
-                      &b3, nullptr, 1, false);
-      bn_backward(h1, OptT(a1), da1[0], OptT(g1), m1, i1, need(ctx, P + 2), need(ctx, P + 3), dg1,
-                  dbe1, &dest, &be1, valid);
-      out[P + 2] = dg1;
-      out[P + 3] = dbe1;
-      out[P + 7] = dW3;
-      out[P + 8] = db3;
-      out[P + 9] = dg4;
-      out[P + 10] = dbe4;
-    };
-    const bool nW = need(ctx, PN) || need(ctx, PE), nB = need(ctx, PN + 1) || need(ctx, PE + 1);
+    Saved sv;
+    load_slots(ctx, sv);
+    const Edges<Pos> ed(ctx);
+    const Pos& pos = ed.pos;
+    const Tensor &xt = sv.xt, &xs = sv.xs, &rowptr = sv.rowptr, &eids = sv.eids, &ei = sv.ei,
+                 &rD = sv.rD, &Wt = sv.Wt, &Ws = sv.Ws;
+    const int64_t N = xt.size(0), E = xs.size(0), d = xt.size(1), dn = sv.n.W0.size(0),
+                  de = sv.e.W0.size(0);
+    variable_list out = ed.grads();
+    const bool nWn = ed.need(pos.n.W0), nWe = ed.need(pos.e.W0), nBn = ed.need(pos.n.b0),
+               nBe = ed.need(pos.e.b0);
+    const bool nW = nWn || nWe, nB = nBn || nBe;
     // TrainStep: every unpack destination deferrable -> the Wt / Ws split
     // reductions are deferred too (their only reader is the deferred unpack)
-    const bool fdef = need(ctx, PN) && need(ctx, PE) && need(ctx, PN + 1) &&
-                      need(ctx, PE + 1) && param_deferrable(sv[30]) && param_deferrable(sv[35]) &&
-                      param_deferrable(sv[31]) && param_deferrable(sv[36]);
+    const bool fdef = nWn && nWe && nBn && nBe && param_deferrable(sv.n.W0) &&
+                      param_deferrable(sv.e.W0) && param_deferrable(sv.n.b0) &&
+                      param_deferrable(sv.e.b0);
     // chain mode (forward under ops.Chains) with every gradient deferred to the
     // flush: the edge half starts without waiting for the main stream (its
     // output gradient comes from the edge chain) and is not joined at the end
@@ -1805,11 +1814,12 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
     }
     dYs.record_stream(fk.main);
     if (chain_b) dYt.record_stream(fk.side);
+    const Tensor dh1s = dYs.narrow(1, 0, de), dh1t = dYt.narrow(1, 0, dn);
     {  // edge side MLP backward on the side stream -> dYs[:, :de]
       TStreamGuard g(fk.side);
-      side_bwd(grads[1], PE, sv[11], sv[12], sv[13], 22, dYs.narrow(1, 0, de), 35, sv[41]);
+      mlp2_backward_tail(sv.e, grads[1], ed, pos.e, out, sv.valid_s, &dh1s);
     }
-    side_bwd(grads[0], PN, sv[8], sv[9], sv[10], 14, dYt.narrow(1, 0, dn), 30, sv[40]);
+    mlp2_backward_tail(sv.n, grads[0], ed, pos.n, out, sv.valid_t, &dh1t);
     fk.side_waits_main();  // side needs dh1_t
     fk.main_waits_side();  // main needs dh1_s
     {  // dP1[e] = rD[i] dh1_t[i] + rD[j] dh1_t[j] -> dYs[:, de:], then the edge GEMM grads
@@ -1837,19 +1847,21 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
       // x_s's gradient added straight into the dense slab's gradient (sink)
       const bool hs = ctx->saved_data.count("gsink_s") > 0;
       const std::vector<Tensor> into_s{hs ? ctx->saved_data["gsink_s"].toTensor() : Tensor()};
-      linear_backward(dYs, {xs}, Ws, nW, nB, {need(ctx, 1)}, dWs, dbs, dxs, nullptr,
+      linear_backward(dYs, {xs}, Ws, nW, nB, {ed.need(pos.x_s)}, dWs, dbs, dxs, nullptr,
                       hs ? &into_s : nullptr, hs ? sink_accumulate(ctx, "gflag_s") : 0, fdef);
     }
     const bool ht = ctx->saved_data.count("gsink_t") > 0;
     const std::vector<Tensor> into_t{ht ? ctx->saved_data["gsink_t"].toTensor() : Tensor()};
-    linear_backward(dYt, {xt}, Wt, nW, nB, {need(ctx, 0)}, dWt, dbt, dxt, nullptr,
+    linear_backward(dYt, {xt}, Wt, nW, nB, {ed.need(pos.x_t)}, dWt, dbt, dxt, nullptr,
                     ht ? &into_t : nullptr, ht ? sink_accumulate(ctx, "gflag_t") : 0, fdef);
     if (!chain_b) fk.main_waits_side();
-    fk.escape({dWs, dbs, dxs[0], out[PE + 2], out[PE + 3], out[PE + 7], out[PE + 8], out[PE + 9],
-               out[PE + 10]});
-    out[0] = dxt[0];
-    out[1] = dxs[0];
+    fk.escape({dWs, dbs, dxs.front(), out[pos.e.g1], out[pos.e.be1], out[pos.e.W3],
+               out[pos.e.b3], out[pos.e.g4], out[pos.e.be4]});
+    out[pos.x_t] = dxt.front();
+    out[pos.x_s] = dxs.front();
     {
+      Tensor &dW0n = out[pos.n.W0], &dW0e = out[pos.e.W0], &db0n = out[pos.n.b0],
+             &db0e = out[pos.e.b0];
       // Wt = [Wn_b; We_a], Ws = [We_b; Wn_a]  (W0 = [W_a | W_b]): unpack the
       // gradients (into the flat bucket when one is set) in one launch
       CopyBlocks cb;
@@ -1857,35 +1869,33 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
         cb.add(src.data_ptr<float>() + r0 * src.stride(0), src.stride(0),
                g.data_ptr<float>() + c0, g.stride(0), rows, d);
       };
-      if (nW && need(ctx, PN)) {
-        out[PN] = grad_like(sv[30]);
-        TORCH_CHECK(out[PN].stride(1) == 1, "hlhgat: gradient of WV_Node[0] not row-major");
-        rows_into(out[PN], dWs, de, dn, 0);
-        rows_into(out[PN], dWt, 0, dn, d);
+      if (nWn) {
+        dW0n = grad_like(sv.n.W0);
+        TORCH_CHECK(dW0n.stride(1) == 1, "hlhgat: gradient of WV_Node[0] not row-major");
+        rows_into(dW0n, dWs, de, dn, 0);
+        rows_into(dW0n, dWt, 0, dn, d);
       }
-      if (nW && need(ctx, PE)) {
-        out[PE] = grad_like(sv[35]);
-        TORCH_CHECK(out[PE].stride(1) == 1, "hlhgat: gradient of WV_Edge[0] not row-major");
-        rows_into(out[PE], dWt, dn, de, 0);
-        rows_into(out[PE], dWs, 0, de, d);
+      if (nWe) {
+        dW0e = grad_like(sv.e.W0);
+        TORCH_CHECK(dW0e.stride(1) == 1, "hlhgat: gradient of WV_Edge[0] not row-major");
+        rows_into(dW0e, dWt, dn, de, 0);
+        rows_into(dW0e, dWs, 0, de, d);
       }
-      if (nB && need(ctx, PN + 1)) {
-        out[PN + 1] = grad_like(sv[31]);
-        cb.add(dbt.data_ptr<float>(), dn, out[PN + 1].data_ptr<float>(), dn, 1, dn);
+      if (nBn) {
+        db0n = grad_like(sv.n.b0);
+        cb.add(dbt.data_ptr<float>(), dn, db0n.data_ptr<float>(), dn, 1, dn);
       }
-      if (nB && need(ctx, PE + 1)) {
-        out[PE + 1] = grad_like(sv[36]);
-        cb.add(dbs.data_ptr<float>(), de, out[PE + 1].data_ptr<float>(), de, 1, de);
+      if (nBe) {
+        db0e = grad_like(sv.e.b0);
+        cb.add(dbs.data_ptr<float>(), de, db0e.data_ptr<float>(), de, 1, de);
       }
       // TrainStep: the unpack joins the deferred work flushed after the backward
-      if (!defer_copies(cb, {out[PN], out[PE], out[PN + 1], out[PE + 1]},
-                        {dWt, dWs, dbt, dbs}, stream_of(xt))) {
+      if (!defer_copies(cb, {dW0n, dW0e, db0n, db0e}, {dWt, dWs, dbt, dbs}, stream_of(xt))) {
         TORCH_CHECK(!fdef, "hlhgat: NodeEdgeInt gradient reductions deferred but the unpack "
                            "could not be (set HLHGAT_DEFER_REDUCE=0)");
         cb.run(stream_of(xt));
       }
     }
-    (void)d;
     return out;
   }
 };
@@ -1898,6 +1908,9 @@ class NEIntValueFn : public torch::autograd::Function<NEIntValueFn> {
 // ---------------------------------------------------------------------------
 class DropoutFn : public torch::autograd::Function<DropoutFn> {
  public:
+  struct Pos {
+    int64_t x;
+  };
   static Tensor forward(AutogradContext* ctx, Tensor x, int64_t T, double s, Tensor state,
                         int64_t site, OptT out) {
     req(x, "x");
@@ -1919,21 +1932,31 @@ class DropoutFn : public torch::autograd::Function<DropoutFn> {
     ctx->saved_data["T"] = T;
     ctx->saved_data["s"] = s;
     ctx->saved_data["site"] = site;
+    EdgeMap em;
+    const Pos pos{em.tensor()};
+    em.other(2);  // T, s
+    em.tensor();  // state
+    em.other();   // site
+    em.opt(out);
+    save_edges(ctx, em, pos);
     ctx->save_for_backward({snap});
     return y;
   }
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    auto sv = ctx->get_saved_variables();
+    const Tensor snap = ctx->get_saved_variables().front();
+    const Edges<Pos> ed(ctx);
     Tensor g = rows2d(grads[0]);
     const int64_t n = g.size(0), d = g.size(1);
     Tensor gx = at::empty({n, d}, g.options());
     chk(hlhgat_dropout_bwd(g.data_ptr<float>(), ld_of(g), n, d,
                            (uint32_t)ctx->saved_data["T"].toInt(),
-                           (float)ctx->saved_data["s"].toDouble(), sv[0].data_ptr<int64_t>(),
+                           (float)ctx->saved_data["s"].toDouble(), snap.data_ptr<int64_t>(),
                            (uint32_t)ctx->saved_data["site"].toInt(), gx.data_ptr<float>(),
                            ld_of(gx), stream_of(g)),
         "dropout_bwd");
-    return {gx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    variable_list grads_in = ed.grads();
+    grads_in[ed.pos.x] = gx;
+    return grads_in;
   }
 };
 
@@ -2296,9 +2319,6 @@ using AttBwdSig = std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor
                                                      double, int64_t);
 using SegSig = Tensor(const Tensor&, const Tensor&, const OptT&, int64_t);
 using SegBwdSig = Tensor(const Tensor&, const Tensor&, const OptT&, int64_t);
-
-inline Tensor opt_or_undef(const OptT& t) { return has(t) ? *t : Tensor(); }
-inline OptT undef_to_opt(const Tensor& t) { return t.defined() ? OptT(t) : OptT(); }
 
 class SpmmOp : public torch::autograd::Function<SpmmOp> {
  public:
