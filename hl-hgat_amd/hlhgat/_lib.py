@@ -42,6 +42,10 @@ SIGNATURES = {
     "hlhgat_mlgc_map": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, P_i64, P_i64]),
     "hlhgat_mlgc_batch": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                   c_vp]),
+    "hlhgat_mlgc_prune": (c_i32, [c_i64, c_i64, C.c_uint32, c_vp, c_vp, c_vp, c_vp, P_i64, P_i64]),
+    "hlhgat_mlgc_device_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "hlhgat_mlgc_device": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
+                                   C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "hlhgat_gather_f32": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "hlhgat_collate_sizes": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "hlhgat_collate": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
@@ -233,6 +237,8 @@ DEVERR_LABEL = 4
 DEVERR_METRIC_LABEL = 8
 DEVERR_METER_FULL = 16
 DEVERR_EIGPE_SIZE = 32
+DEVERR_MLGC_RANGE = 64
+MLGC_ONE_WAY, MLGC_PRUNE_SINGLE, MLGC_DROP_ISOLATED = 1, 2, 4
 LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
 CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
 LOSS_ONE_LAUNCH_MAX = 16384  # up to here the loss forwards need no workspace

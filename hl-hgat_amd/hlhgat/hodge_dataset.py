@@ -24,7 +24,8 @@ import torch
 __all__ = ["PairData", "Batch", "collate", "adj2par1", "BoundaryOperator", "degree",
            "hodge_laplacians", "dense_to_sparse", "is_sorted_symmetric", "locality_order",
            "static_caps", "pad_batch", "level_caps", "pad_levels", "PackedGraphs", "halo_tiles", "graclus", "mlgc", "mlgc_weighted", "mlgc_map", "to_undirected_mean",
-           "hodge_factor_ok", "hodge_coo_from_boundary", "fc2mask"]
+           "hodge_factor_ok", "hodge_coo_from_boundary", "fc2mask", "mlgc_prune", "mlgc_weight",
+           "brain_levels"]
 
 _INC_KEYS = ("edge_index_s", "edge_index_t", "edge_index", "row_order_s", "row_order_t")
 _HODGE_KEYS = ("edge_index_s", "edge_index_t")
@@ -1303,6 +1304,115 @@ def mlgc_weighted(g: "PairData", seed: int = 0):
     c_node, c_edge, ei1, n1 = mlgc_map(lab, np.asarray(g.edge_index))
     return (_mlgc_level(ei1, n1), torch.from_numpy(c_node.astype(np.float32)).view(-1, 1),
             torch.from_numpy(c_edge).view(-1, 1))
+
+
+def mlgc_prune(c_node, c_edge, coarse_edge_index, n1: int, prune_single: bool = True,
+               drop_isolated: bool = True):
+    """MLGC_Weight's two pruning passes (HL-HGAT-DEMO/lib/Hodge_Dataset.py:
+    222-241) on mlgc_map's outputs, by the native host builder
+    (hlhgat_mlgc_prune).  prune_single: a coarse edge that one fine edge alone
+    supports is removed (that edge's c_edge becomes inf), the others keep
+    their order and are renumbered.  drop_isolated (after it): a coarse node
+    no remaining coarse edge touches is removed (its fine nodes get c_node
+    inf), the other ids close up.
+    Returns (c_node float32 [n], c_edge float32 [E], coarse edge_index int64
+    [2, E1'], n1')."""
+    import ctypes as C
+    from ._lib import LIB, MLGC_DROP_ISOLATED, MLGC_PRUNE_SINGLE, check
+    cn = np.ascontiguousarray(np.asarray(c_node, dtype=np.int64).reshape(-1))
+    ce = np.array(np.asarray(c_edge, dtype=np.float32).reshape(-1))  # a copy: pruned in place
+    ei1 = np.asarray(coarse_edge_index, dtype=np.int64).reshape(2, -1)
+    n, E = cn.size, ce.size
+    e1 = np.zeros((2, max(E, 1)), dtype=np.int64)
+    e1[:, :ei1.shape[1]] = ei1
+    out = np.empty(n, dtype=np.float32)
+    n1_, ne = C.c_int64(int(n1)), C.c_int64(int(ei1.shape[1]))
+    flags = (MLGC_PRUNE_SINGLE if prune_single else 0) | (MLGC_DROP_ISOLATED if drop_isolated else 0)
+    # the row stride of the coarse edge buffer is E (hlhgat_mlgc_map's layout)
+    buf = np.ascontiguousarray(e1[:, :E]) if E else e1
+    check(LIB.hlhgat_mlgc_prune(n, E, flags, cn.ctypes.data, out.ctypes.data, ce.ctypes.data,
+                                buf.ctypes.data, C.byref(n1_), C.byref(ne)), "mlgc_prune")
+    return out, ce, np.ascontiguousarray(buf[:, :ne.value]), int(n1_.value)
+
+
+def _pool_edges_mean(x_s: torch.Tensor, c_edge: np.ndarray, E1: int) -> torch.Tensor:
+    """torch_scatter.scatter_mean(x_s[finite], c_edge[finite], dim=0) as
+    MLGC_Weight pools the edge signal (HL-HGAT-DEMO/lib/Hodge_Dataset.py:
+    256-258): sums in entry order, then / count."""
+    x = torch.as_tensor(x_s).to(torch.float32)
+    x = x.reshape(x.shape[0], -1)
+    keep = torch.from_numpy(~np.isinf(c_edge))
+    pos = torch.from_numpy(c_edge)[keep].to(torch.long)
+    xs = x[keep]
+    s = torch.zeros(E1, x.shape[1]).scatter_add_(0, pos.view(-1, 1).expand(-1, x.shape[1]), xs)
+    cnt = torch.zeros(E1).scatter_add_(0, pos, torch.ones(pos.numel()))
+    return s / cnt.view(-1, 1)
+
+
+def mlgc_weight(g: "PairData", seed: int = 0, perm=None, device=None):
+    """MLGC_Weight (HL-HGAT-DEMO/lib/Hodge_Dataset.py:181-268), the brain
+    model's coarsening: graclus on the graph's own i<j edges ONE WAY, as given
+    (a node can only pick a partner among its higher-numbered neighbours),
+    weighted by x_s.view(-1) -- a negative weight never matches --, the fine ->
+    coarse map, then both pruning passes (mlgc_prune); the coarse x_s is the
+    scatter_mean of the kept fine edges' x_s, x_t is ones.
+    perm: graclus's node order (default: the seeded permutation of graclus).
+    device: None runs the native host builders; a ROCm device runs the
+    matching, the map and the pruning in one launch (ops.mlgc_device) and the
+    edge pooling through hodge_cheb_conv.cluster_mean -- the same maps bit for
+    bit, x_s up to fp32 summation order.
+    Returns (coarse PairData, c_node [n, 1] float, c_edge [E, 1] float)."""
+    n = int(g.num_node1)
+    ei = np.ascontiguousarray(np.asarray(torch.as_tensor(g.edge_index).cpu(), dtype=np.int64))
+    x_s = torch.as_tensor(g.x_s).cpu()
+    w = np.asarray(x_s, dtype=np.float32).reshape(-1)
+    if w.size != ei.shape[1]:
+        raise ValueError("mlgc_weight: x_s must hold one weight per edge")
+    if perm is None:
+        perm = np.random.default_rng(seed).permutation(n)
+    perm = np.ascontiguousarray(np.asarray(perm, dtype=np.int64))
+    if device is None:
+        lab = graclus(ei, n, weight=w, perm=perm)
+        c_node, c_edge, ei1, n1 = mlgc_map(lab, ei)
+        c_node, c_edge, ei1, n1 = mlgc_prune(c_node, c_edge, ei1, n1)
+        pooled = _pool_edges_mean(x_s, c_edge, ei1.shape[1])
+    else:
+        from . import ops
+        from .hodge_cheb_conv import cluster_mean
+        dev = torch.device(device)
+        E = ei.shape[1]
+        ints = torch.from_numpy(np.concatenate([ei.reshape(-1), perm, [0, n, 0, E]])).to(dev)
+        ei_d = ints[:2 * E].view(2, E)
+        r = ops.mlgc_device(ei_d, ints[2 * E + n:2 * E + n + 2], ints[2 * E + n + 2:],
+                            ints[2 * E:2 * E + n], weight=torch.from_numpy(w.astype(np.float64)).to(dev),
+                            one_way=True, prune_single=True, drop_isolated=True)
+        n1, E1 = (int(v) for v in torch.cat([r.cn, r.cm]).cpu())  # the one read-back
+        pooled = cluster_mean(x_s.to(dev, torch.float32).reshape(E, -1), r.c_edge, E1).cpu()
+        ops.check_device_errors()
+        c_node, c_edge = r.c_node.cpu().numpy(), r.c_edge.cpu().numpy()
+        ei1 = np.ascontiguousarray(r.ce[:, :E1].cpu().numpy())
+    coarse = _mlgc_level(ei1, n1)
+    coarse.x_s = pooled
+    return (coarse, torch.from_numpy(c_node).view(-1, 1), torch.from_numpy(c_edge).view(-1, 1))
+
+
+def brain_levels(fine: "PairData", pool_num: int = 2, seed: int = 0, perms=None, device=None):
+    """The brain model's level list as the DEMO notebook precomputes it
+    (OHBM_DEMO.ipynb, "precompute pooling": graphs = [graph]; for i in
+    range(pool_num): graph, c_node, c_edge = MLGC_Weight(graphs[i]);
+    graphs[i].pos_s, graphs[i].pos_t = c_edge, c_node; graphs.append(graph)).
+    Returns [fine, coarse1, ...]; every level p < pool_num (fine included, as
+    in the notebook) gets pos_s / pos_t set.  Level p's graclus order is
+    perms[p] or the permutation seeded with seed + p.  device: see
+    mlgc_weight.  pipeline.BrainPipeline(levels=...) takes the result."""
+    levels = [fine]
+    for p in range(int(pool_num)):
+        coarse, c_node, c_edge = mlgc_weight(levels[p], seed=seed + p,
+                                             perm=None if perms is None else perms[p],
+                                             device=device)
+        levels[p].pos_s, levels[p].pos_t = c_edge, c_node
+        levels.append(coarse)
+    return levels
 
 
 def fc2mask(FC: torch.Tensor, threshmode: int = 1, k_ratio: float = 0.25) -> torch.Tensor:

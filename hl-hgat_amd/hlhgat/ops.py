@@ -35,7 +35,7 @@ __all__ = [
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
     "bce_logits_loss", "cross_entropy", "mse_loss", "average_precision",
     "collect_rows", "f1_per_graph", "argmax_correct", "regression_summary",
-    "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared",
+    "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared", "mlgc_device",
     "POLY_LAGUERRE", "POLY_CHEB", "POLY_LAGUERRE_DEMO", "SIGMA_SIGMOID", "SIGMA_RELU",
 ]
 
@@ -661,6 +661,61 @@ def eig_pe(edge_index: torch.Tensor, node_counts, k: int, max_nodes: Optional[in
                             int(max_nodes), k, pe.data_ptr(), k - 1, lmax.data_ptr(), ws.data_ptr(),
                             wsb, _stream(ei)), "eig_pe")
     return pe, lmax
+
+
+def mlgc_device(edge_index: torch.Tensor, node_ptr: torch.Tensor, edge_ptr: torch.Tensor,
+                perm: torch.Tensor, weight: Optional[torch.Tensor] = None, one_way: bool = False,
+                prune_single: bool = False, drop_isolated: bool = False):
+    """One MLGC level for a whole batch on the device, in one launch
+    (hlhgat_mlgc_device: the graclus visit loop, the fine -> coarse maps and
+    MLGC_Weight's pruning passes; lib/Hodge_Dataset.py:252-275, HL-HGAT-DEMO/
+    lib/Hodge_Dataset.py:193-241) -- hodge_dataset.mlgc_batch_flat (and
+    mlgc_prune) bit for bit.  edge_index int64 [2, E] (i < j, PairData
+    offsets; its cached incidence CSR gives the neighbour lists), node_ptr /
+    edge_ptr int64 [G + 1] and perm int64 [N] (local ids per graph) on the
+    device, weight float64 [E] or None (ones).  one_way: the matching sees an
+    edge from its first end only (MLGC_Weight).  Nothing is read back.
+    Returns a hodge_dataset.MLGCBatch of device tensors: c_node float32 [N],
+    c_edge float32 [E], ce int64 [2, E] (graph g's local coarse edges at the
+    head of its edge slot), cn / cm int64 [G].  Edges or perm entries outside
+    their graph raise HLHGAT_DEVERR_MLGC_RANGE (check_device_errors)."""
+    from .hodge_dataset import MLGCBatch
+    _req_dev(edge_index, "edge_index", torch.int64)
+    _req_dev(node_ptr, "node_ptr", torch.int64)
+    _req_dev(edge_ptr, "edge_ptr", torch.int64)
+    _req_dev(perm, "perm", torch.int64)
+    if weight is not None:
+        _req_dev(weight, "weight", torch.float64)
+    dev = edge_index.device
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise RuntimeError(f"hlhgat: edge_index must be [2, E] (got {tuple(edge_index.shape)})")
+    G = node_ptr.numel() - 1
+    if G < 0 or edge_ptr.numel() != G + 1:
+        raise RuntimeError("hlhgat: mlgc_device: node_ptr and edge_ptr must both have G + 1 entries")
+    N, E = perm.numel(), edge_index.size(1)
+    if weight is not None and weight.numel() != E:
+        raise RuntimeError(f"hlhgat: mlgc_device: weight has {weight.numel()} entries, expected {E}")
+    inc = incidence(edge_index, N)
+    ei = inc.edge_index
+    node_ptr, edge_ptr, perm = node_ptr.contiguous(), edge_ptr.contiguous(), perm.contiguous()
+    weight = None if weight is None else weight.contiguous()
+    c_node = torch.empty(N, dtype=torch.float32, device=dev)
+    c_edge = torch.empty(E, dtype=torch.float32, device=dev)
+    ce = torch.zeros(2, E, dtype=torch.int64, device=dev)
+    cn = torch.empty(G, dtype=torch.int64, device=dev)
+    cm = torch.empty(G, dtype=torch.int64, device=dev)
+    wsb = int(LIB.hlhgat_mlgc_device_workspace_bytes(N, E, G))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    flags = ((_lib.MLGC_ONE_WAY if one_way else 0) | (_lib.MLGC_PRUNE_SINGLE if prune_single else 0)
+             | (_lib.MLGC_DROP_ISOLATED if drop_isolated else 0))
+    check(LIB.hlhgat_mlgc_device(G, node_ptr.data_ptr(), edge_ptr.data_ptr(), inc.rowptr.data_ptr(),
+                                 inc.edge_ids.data_ptr() if E else None,
+                                 ei.data_ptr() if E else None, E, N, _ptr(weight),
+                                 perm.data_ptr() if N else None, flags,
+                                 c_node.data_ptr() if N else None, c_edge.data_ptr() if E else None,
+                                 ce.data_ptr() if E else None, cn.data_ptr(), cm.data_ptr(),
+                                 ws.data_ptr(), wsb, _stream(ei)), "mlgc_device")
+    return MLGCBatch(node_ptr, edge_ptr, c_node, c_edge, ce, cn, cm)
 
 
 def copy_words_batched(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor]) -> None:
@@ -3145,6 +3200,9 @@ _DEVERR_TEXT = {
                           "launches); that launch's statistics are not trusted",
     _lib.DEVERR_EIGPE_SIZE: "eig_pe: a graph has more nodes than max_nodes (which sized its "
                             "workspace slice); its pe rows are zero and its lmax is 0",
+    _lib.DEVERR_MLGC_RANGE: "mlgc_device: an edge end outside its graph's node range, a perm "
+                            "entry outside [0, n) or graph offsets that leave the arrays; the "
+                            "offender was treated as absent",
 }
 
 

@@ -103,11 +103,21 @@ class SuperpixelPipeline:
     graphs: raw samples (x, pos, edge_index, edge_attr, y; superpixel_raw).
     keig: the dataset's keig (the reference's trainset uses keig + 1 = 11,
       main_cifar10SP...:206; eig_pe is called with k=10 -> 9 PE columns).
-    aug: dropout_edge augmentation as the reference's training set."""
+    aug: dropout_edge augmentation as the reference's training set.
+    mlgc: "host" (default) runs graclus and the fine -> coarse map on host
+      threads before the upload (hlhgat_mlgc_batch); "device" runs them after
+      the upload in one launch (ops.mlgc_device: the node orders travel in the
+      int64 upload, the coarse counts come back in ONE device -> host read to
+      size the coarse level, the coarse edges are compacted on the device) --
+      the same batches bit for bit.  device="cpu" always takes the host path."""
 
     NODE_DIM, EDGE_DIM = 5, 4
 
-    def __init__(self, graphs: Sequence, keig: int = 11, aug: bool = True, pe_k: int = 10):
+    def __init__(self, graphs: Sequence, keig: int = 11, aug: bool = True, pe_k: int = 10,
+                 mlgc: str = "host"):
+        if mlgc not in ("host", "device"):
+            raise ValueError(f"SuperpixelPipeline: mlgc must be 'host' or 'device' (got {mlgc!r})")
+        self.mlgc = mlgc
         self.keig = keig
         self.aug = aug
         self.pe_k = pe_k
@@ -200,7 +210,8 @@ class SuperpixelPipeline:
         # MLGC on the host: graclus on L0's pattern (= the edges, both ways; its
         # self-loops are dropped by graclus) with unit weights, the fine -> coarse map
         # (all graphs in one native call on host threads: hlhgat_mlgc_batch)
-        mg = mlgc_batch_flat(ei, E_g, ns, perm)
+        on_host = self.mlgc == "host" or str(device) == "cpu"
+        mg = mlgc_batch_flat(ei, E_g, ns, perm) if on_host else None
         self._tick("MLGC (native batch)")
         if str(device) == "cpu":
             e_off = np.concatenate([[0], np.cumsum(E_g)])
@@ -208,7 +219,8 @@ class SuperpixelPipeline:
             attrs = [attr[e_off[b]:e_off[b + 1]] for b in range(len(idx))]
             lv0, lv1 = self._levels_host(idx, eis, attrs, [int(n) for n in ns], mg.per_graph())
         else:
-            lv0, lv1 = self._levels_device(idx, ei, attr, ns, E_g, gid_e, mg, torch.device(device))
+            lv0, lv1 = self._levels_device(idx, ei, attr, ns, E_g, gid_e, mg, torch.device(device),
+                                           perm)
         # sign flips of the PE columns (after the cluster column is prepended),
         # one row of signs per graph broadcast over its nodes / edges
         B = len(idx)
@@ -292,37 +304,33 @@ class SuperpixelPipeline:
                                              torch.as_tensor([e.shape[1] for e in eis]))
         return lv0, collate(f1, check_hodge=False)
 
-    def _levels_device(self, idx, ei, attr, ns, E_g, gid_e, mg, dev):
+    def _levels_device(self, idx, ei, attr, ns, E_g, gid_e, mg, dev, perm=None):
         """Both levels on the device.  The host arrays travel in two
         asynchronous uploads from pinned memory (one int64, one float32; the
         device tensors are views of them); the Hodge builder gets its sizes from the host (the nnz of L0
         and L1 follow from the degrees), so nothing here waits on the device
-        but the eigh's own error check."""
+        but the eigh's own error check.  mg None (mlgc="device"): MLGC runs
+        here after the upload (ops.mlgc_device), its coarse counts are read
+        back once and the coarse Hodge builder sizes itself on the device."""
         from . import ops
         B = len(idx)
         N, E = int(ns.sum()), int(ei.shape[1])
         n_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
         gid_n = np.repeat(np.arange(B), ns)
         ei_b = ei + n_off[gid_e]  # block-diagonal batch (PairData offsets)
+        e_off = np.concatenate([[0], np.cumsum(E_g)]).astype(np.int64)
+        nodes = self._segments(self.n_off[idx], ns)
+        if mg is None:
+            return self._levels_device_mlgc(idx, ei_b, attr, ns, E_g, gid_n, gid_e, n_off, e_off,
+                                            nodes, perm, dev)
         # coarse level: each graph's coarse edges at the head of its edge slot
         n1 = mg.cn
         m1 = mg.cm
         o1 = np.concatenate([[0], np.cumsum(n1)]).astype(np.int64)
-        e_off = np.concatenate([[0], np.cumsum(E_g)]).astype(np.int64)
         cidx = self._segments(e_off[:-1], m1)
         gid_c = np.repeat(np.arange(B), m1)
         ei1 = mg.ce[:, cidx] + o1[gid_c]
         N1, E1 = int(o1[-1]), int(ei1.shape[1])
-        nodes = self._segments(self.n_off[idx], ns)
-
-        def nnz(e, n):
-            # the degree formulas (and the Laplacians themselves) assume a
-            # simple graph: unique edges with i < j
-            if e.shape[1] and ((e[0] >= e[1]).any() or
-                               np.unique(e[0] * n + e[1]).size != e.shape[1]):
-                raise ValueError("hlhgat: coarse edges are not unique i < j pairs")
-            deg = np.bincount(e.reshape(-1), minlength=n)
-            return int((deg > 0).sum()) + 2 * e.shape[1], int((deg * deg).sum()) - e.shape[1]
         ints = [ei_b.reshape(-1), ei1.reshape(-1), ns, E_g, n1, m1,
                 self.y_all.numpy()[idx].astype(np.int64), gid_n, gid_e]
         flts = [self.x_all[nodes].reshape(-1), self.pos_all[nodes].reshape(-1), attr,
@@ -342,6 +350,64 @@ class SuperpixelPipeline:
         x, pos, attr_d, c_node, c_edge = cut(fdev, [a.size for a in flts])
         x, pos = x.view(N, 3), pos.view(N, 2)
         self._tick("device levels: edge upload")
+        return self._levels_finish(ns, ei_b, ei_d, ns_d, Eg_d, y_d, gid_d, gide_d, x, pos, attr_d,
+                                   c_node, c_edge, ei1_d, n1_d, m1_d, N1, E1,
+                                   (N1,) + self._nnz(ei1, N1), dev)
+
+    @staticmethod
+    def _nnz(e, n):
+        """(nnz(L0), nnz(L1)) from the degrees.  The formulas (and the
+        Laplacians themselves) assume a simple graph: unique edges with i < j."""
+        if e.shape[1] and ((e[0] >= e[1]).any() or
+                           np.unique(e[0] * n + e[1]).size != e.shape[1]):
+            raise ValueError("hlhgat: coarse edges are not unique i < j pairs")
+        deg = np.bincount(e.reshape(-1), minlength=n)
+        return int((deg > 0).sum()) + 2 * e.shape[1], int((deg * deg).sum()) - e.shape[1]
+
+    def _levels_device_mlgc(self, idx, ei_b, attr, ns, E_g, gid_n, gid_e, n_off, e_off, nodes,
+                            perm, dev):
+        """mlgc="device": the upload carries the node orders and the graph
+        offsets instead of the host's coarse maps; MLGC runs on the device."""
+        from . import ops
+        B = len(idx)
+        N, E = int(ns.sum()), int(ei_b.shape[1])
+        ints = [ei_b.reshape(-1), ns, E_g, self.y_all.numpy()[idx].astype(np.int64), gid_n, gid_e,
+                np.asarray(perm, np.int64), n_off, e_off]
+        flts = [self.x_all[nodes].reshape(-1), self.pos_all[nodes].reshape(-1), attr]
+        idev = _h2d(np.concatenate(ints), dev)
+        fdev = _h2d(np.concatenate(flts), dev)
+        o, cuts = 0, []
+        for a in ints:
+            cuts.append(idev[o:o + a.size])
+            o += a.size
+        ei_d, ns_d, Eg_d, y_d, gid_d, gide_d, perm_d, nptr_d, eptr_d = cuts
+        ei_d = ei_d.view(2, E)
+        x, pos, attr_d = fdev[:3 * N].view(N, 3), fdev[3 * N:5 * N].view(N, 2), fdev[5 * N:]
+        self._tick("device levels: edge upload")
+        r = ops.mlgc_device(ei_d, nptr_d, eptr_d, perm_d)
+        n1_d, m1_d = r.cn, r.cm
+        # the one read-back: the coarse level's sizes
+        N1, E1 = (int(v) for v in torch.stack([n1_d.sum(), m1_d.sum()]).cpu())
+        # compact each graph's coarse edges (the head of its edge slot) to
+        # [2, E1] and add the coarse PairData offsets
+        gid_c = torch.repeat_interleave(torch.arange(B, device=dev), m1_d, output_size=E1)
+        c_off = torch.cumsum(m1_d, 0) - m1_d
+        o1 = torch.cumsum(n1_d, 0) - n1_d
+        src = torch.arange(E1, device=dev) - c_off[gid_c] + eptr_d[:-1][gid_c]
+        ei1_d = r.ce[:, src] + o1[gid_c]
+        self._tick("device levels: MLGC (device)")
+        return self._levels_finish(ns, ei_b, ei_d, ns_d, Eg_d, y_d, gid_d, gide_d, x, pos, attr_d,
+                                   r.c_node, r.c_edge, ei1_d, n1_d, m1_d, N1, E1, None, dev)
+
+    def _levels_finish(self, ns, ei_b, ei_d, ns_d, Eg_d, y_d, gid_d, gide_d, x, pos, attr_d, c_node,
+                       c_edge, ei1_d, n1_d, m1_d, N1, E1, sizes1, dev):
+        """The device stages after the upload (and MLGC): eig_pe, both Hodge
+        builds, the features.  sizes1: the coarse builder's host sizes, or
+        None (it then reads its own row sizes)."""
+        from . import ops
+        nnz = self._nnz
+        B = len(ns)
+        N, E = int(ns.sum()), int(ei_b.shape[1])
         # eig_pe and lambda_max of every graph in one launch (hlhgat_eig_pe:
         # fp64 Lanczos with full re-orthogonalisation per graph), then the
         # Hodge Laplacians with that lambda_max
@@ -378,7 +444,7 @@ class SuperpixelPipeline:
         lv0.num_nodes = N
         lv0._gid_t, lv0._gid_s = gid_d, gide_d
         self._tick("device levels: features")
-        c_t, c_wt, c_s, c_ws, _ = ops.hodge_build(ei1_d, n1_d, sizes=(N1,) + nnz(ei1, N1))
+        c_t, c_wt, c_s, c_ws, _ = ops.hodge_build(ei1_d, n1_d, sizes=sizes1)
         self._tick("device levels: Hodge build (coarse)")
         lv1 = Batch()
         lv1.num_graphs = B

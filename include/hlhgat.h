@@ -185,6 +185,79 @@ int hlhgat_mlgc_batch(int64_t n_graphs, const int64_t* node_ptr, const int64_t* 
                       float* c_edge, int64_t* coarse_edges, int64_t* coarse_n,
                       int64_t* coarse_e);
 
+/* Flags of hlhgat_mlgc_prune / hlhgat_mlgc_device. */
+/* the matching sees each edge from its first end only (MLGC_Weight passes
+ * graclus the i<j list one way, HL-HGAT-DEMO/lib/Hodge_Dataset.py:193-194);
+ * without it, both ways (MLGC / MLGC_weighted, lib/Hodge_Dataset.py:252, :311) */
+#define HLHGAT_MLGC_ONE_WAY 1u
+/* remove the coarse edges that exactly one fine edge supports
+ * (HL-HGAT-DEMO/lib/Hodge_Dataset.py:222-230) */
+#define HLHGAT_MLGC_PRUNE_SINGLE 2u
+/* then remove the coarse nodes no remaining coarse edge touches
+ * (HL-HGAT-DEMO/lib/Hodge_Dataset.py:234-241) */
+#define HLHGAT_MLGC_DROP_ISOLATED 4u
+
+/* HOST function.  The two pruning passes of the DEMO's MLGC_Weight
+ * (HL-HGAT-DEMO/lib/Hodge_Dataset.py:222-241) on hlhgat_mlgc_map's outputs:
+ * c_node_in [n_nodes] (int64 ranks), c_edge [n_edges] and coarse_edges
+ * [2][n_edges capacity] in place, *n_coarse_nodes / *n_coarse_edges in and
+ * out; c_node [n_nodes] out as float32 (the reference's dtype; ids stay
+ * exact: n_nodes, n_edges < 2^24 is an argument check).
+ * HLHGAT_MLGC_PRUNE_SINGLE: a coarse edge that exactly one fine edge maps to
+ * is removed and that fine edge's c_edge becomes +inf; the remaining coarse
+ * edges keep their first-seen order and are renumbered from 0, every finite
+ * c_edge with them.  HLHGAT_MLGC_DROP_ISOLATED (after the pruning): a coarse
+ * node that ends no remaining coarse edge is removed, the fine nodes mapped to
+ * it get c_node = +inf, the other ids drop by the number of removed ids below
+ * them and the coarse edges are relabelled (PyG remove_isolated_nodes).  No
+ * flag: c_node = (float)c_node_in, nothing else changes.
+ * The reference keys a coarse edge by the float imax + 0.0001 * imin (:207);
+ * the integer pair keys used here are equivalent while a level has fewer than
+ * 10^4 coarse nodes (beyond that the reference's keys collide, these do not). */
+int hlhgat_mlgc_prune(int64_t n_nodes, int64_t n_edges, unsigned flags, const int64_t* c_node_in,
+                      float* c_node, float* c_edge, int64_t* coarse_edges,
+                      int64_t* n_coarse_nodes, int64_t* n_coarse_edges);
+
+/* ---- multi-level graph coarsening on the device --------------------------
+ * One MLGC level for a batch of graphs in ONE launch, one workgroup per
+ * graph: the graclus visit loop (torch_cluster graclus_cluster as MLGC calls
+ * it, lib/Hodge_Dataset.py:252-253, :311; HL-HGAT-DEMO/lib/Hodge_Dataset.py:
+ * 193-194), the fine -> coarse maps (lib/Hodge_Dataset.py:254-275;
+ * HL-HGAT-DEMO :195-216) and MLGC_Weight's pruning passes (HL-HGAT-DEMO
+ * :222-241) -- hlhgat_mlgc_batch (+ hlhgat_mlgc_prune per graph) on device
+ * pointers, bit for bit.
+ * edge_index: int64 [2][n_edges], the batch's i<j list with PairData offsets
+ * (global node ids); graph g's edges are [edge_ptr[g], edge_ptr[g+1]), its
+ * nodes [node_ptr[g], node_ptr[g+1]).  inc_rowptr / inc_edge: the batch's
+ * incidence CSR (hlhgat_incidence_csr over n_nodes) -- the neighbour lists.
+ * weight: [n_edges] per edge or NULL (ones).  perm: [n_nodes], graph g's visit
+ * order as LOCAL ids in its node slot.  flags: HLHGAT_MLGC_*.
+ * Outputs are local to each graph, in hlhgat_mlgc_batch's layout: c_node
+ * [n_nodes] and c_edge [n_edges] as float32 (+inf: a contracted or pruned
+ * edge, a dropped node), graph g's coarse edges (local coarse ids) at the
+ * head of its edge slot of coarse_edges [2][n_edges] (the rest of the slot is
+ * unspecified), coarse_n[g] / coarse_e[g] its coarse counts.
+ * Matching: nodes in perm order; an unmatched node u takes, among its
+ * unmatched neighbours with weight >= 0, the largest weight and among equals
+ * the largest id (with unique pairs, the host's "last neighbour in ascending
+ * column order with w >= best so far"; NaN never matches); both get id
+ * min(u, v); with no candidate u keeps id u.
+ * Preconditions: unique edge pairs, i < j, per graph n, m < 2^24.  An edge
+ * with an end outside its graph's node range (or listed in the incidence of a
+ * node of another graph) is treated as absent (c_edge +inf where it lies in
+ * the graph's own slot), a perm entry outside [0, n) is skipped, a graph whose
+ * offsets leave the arrays or the workspace is left with zero counts; each
+ * raises HLHGAT_DEVERR_MLGC_RANGE and nothing is written out of bounds.
+ * Per-graph state lives in LDS when it fits (64 KiB), else in the graph's
+ * slice of workspace; the results are the same bits either way. */
+size_t hlhgat_mlgc_device_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t n_graphs);
+int hlhgat_mlgc_device(int64_t n_graphs, const int64_t* node_ptr, const int64_t* edge_ptr,
+                       const int32_t* inc_rowptr, const int32_t* inc_edge,
+                       const int64_t* edge_index, int64_t n_edges, int64_t n_nodes,
+                       const double* weight, const int64_t* perm, unsigned flags, float* c_node,
+                       float* c_edge, int64_t* coarse_edges, int64_t* coarse_n,
+                       int64_t* coarse_e, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- native data loader (HOST functions, host pointers) -----------------
  * Replaces the reference's per-step DataLoader collation of PairData
  * (lib/Hodge_Dataset.py:40-48; main_zinc_HL_HGCNN_dense_int3_pyr.py:223-225)
@@ -1086,6 +1159,10 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
 /* hlhgat_eig_pe: a graph has more nodes than the caller's max_nodes (which
  * sized its workspace slice); its pe rows are zero and its lmax is 0 */
 #define HLHGAT_DEVERR_EIGPE_SIZE 32u
+/* hlhgat_mlgc_device: an edge end outside its graph's node range, a perm entry
+ * outside [0, n), or graph offsets that leave the arrays / the workspace; the
+ * offender was treated as absent */
+#define HLHGAT_DEVERR_MLGC_RANGE 64u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 
