@@ -44,6 +44,7 @@
 // drained by vmcnt(0) before a barrier; one lane takes a relaxed agent atomic
 // ticket; readers use agent-scope atomic loads.
 #include "gemm_core.h"
+#include "proj_bf16.h"
 
 #include <atomic>
 
@@ -2046,6 +2047,10 @@ extern "C" int hlhgat_proj_bn_fwd(int nblocks, const float* const* A, const int6
     const int64_t cap = capacity_of(reinterpret_cast<const void*>(k_proj_bn_fwd<false>));
     fused = (int64_t)gx * gy <= cap;
   }
+  // bf16 mode: the bf16 projection, then the fp32 BatchNorm kernels
+  if (fused && gemm_precision() == HLHGAT_GEMM_BF16 &&
+      gemm_bf16_operands_ok(nblocks, A, lda, kb, N) && gemm_bf16_operands_ok(nblocks, W, ldw, kb, N))
+    fused = false;
   if (!fused) {
     const int rc = hlhgat_proj_fwd(nblocks, A, lda, W, ldw, kb, M, N, bias, x, ldx, 0, stream);
     if (rc != HLHGAT_OK) return rc;

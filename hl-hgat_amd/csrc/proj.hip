@@ -17,6 +17,8 @@
 // the kernels stream A straight into registers (each row read once, W served
 // from L1/L2), 4 waves per workgroup stacked along M.
 #include "gemm_core.h"
+#include "proj_args.h"
+#include "proj_bf16.h"
 
 #include <atomic>
 #include <cstdio>
@@ -173,20 +175,7 @@ __global__ __launch_bounds__(256) void k_proj_fwd_lds(FwdArgs a) {
 // ---------------------------------------------------------------------------
 // data gradient: dA_b = dC W_b   (reduction over N)
 // ---------------------------------------------------------------------------
-struct BwdDataArgs {
-  int nb;
-  int N;
-  int64_t M;
-  const float* G;
-  int64_t ldg;
-  const float* W[MAXB];
-  float* O[MAXB];
-  int64_t ldw[MAXB];
-  int64_t ldo[MAXB];
-  int kb[MAXB];
-  int tile_start[MAXB + 1];
-  int accumulate;
-};
+// (BwdDataArgs: proj_args.h)
 
 template <int TM, int TN, bool VEC>
 __global__ __launch_bounds__(256) void k_proj_bwd_data(BwdDataArgs a) {
@@ -463,24 +452,7 @@ constexpr int WT_TN = 4;  // 64 cols of k per tile
 constexpr int WT_ROWS = WT_TM * 16;
 constexpr int WT_COLS = WT_TN * 16;
 
-struct BwdWeightArgs {
-  int nb;
-  int N;
-  int64_t M;
-  const float* G;
-  int64_t ldg;
-  const float* A[MAXB];
-  int64_t lda[MAXB];
-  int kb[MAXB];
-  int tile_start[MAXB + 1];
-  int64_t part_off[MAXB];
-  int64_t bias_off;  // -1: no bias gradient
-  int64_t part_stride;
-  float* part;
-  int64_t rows_per_split;
-  int tiles_n;
-  int xcd_map;  // remap (tile, split) so each XCD walks one contiguous range of them
-};
+// (BwdWeightArgs: proj_args.h)
 
 __global__ __launch_bounds__(256) void k_proj_bwd_weight(BwdWeightArgs a) {
   __shared__ float red[4][WT_TM * WT_TN * 4][64];
@@ -1217,6 +1189,13 @@ constexpr int data_xcd_map() { return 1; }
 // (+1.3 % at the ZINC step against 32-column tiles, same-box A/B)
 constexpr int bwd_tnd() { return 4; }
 
+// bf16 eligibility of a gradient call: dC and the operand blocks P (W for the
+// data gradient, A for the weight gradient)
+bool bf16_grad_ok(const float* dC, int64_t lddc, int nb, const float* const* P, const int64_t* ld,
+                  const int64_t* kb, int64_t N) {
+  return aligned16(dC) && (lddc % 4) == 0 && gemm_bf16_operands_ok(nb, P, ld, kb, N);
+}
+
 bool vec_ok(const float* p, int64_t ld, int64_t kb) {
   return aligned16(p) && (ld % 4) == 0 && (kb % 4) == 0;
 }
@@ -1289,6 +1268,12 @@ extern "C" int hlhgat_proj_fwd(int nblocks, const float* const* A,
   double bytes = 4.0 * (double)M * N;
   for (int b = 0; b < nblocks; ++b) bytes += 4.0 * (double)M * kb[b] + 4.0 * N * kb[b];
   ProfScope prof(HLHGAT_PROF_PROJ, s, bytes, flops);
+  if (gemm_precision() == HLHGAT_GEMM_BF16 &&
+      gemm_bf16_route(gemm_bf16_operands_ok(nblocks, A, lda, kb, N) &&
+                      gemm_bf16_operands_ok(nblocks, W, ldw, kb, N))) {
+    a.xcd_map = M >= 65536 ? fwd_xcd_map() : 0;
+    return launch_proj_fwd_bf16(&a, tn, s, &prof);
+  }
   if (vec && big_fwd_ok(M, N, ktot)) {
     const int cfg = big_fwd_cfg(N);
     int rows, cols;
@@ -1363,6 +1348,9 @@ extern "C" int hlhgat_proj_bwd_data(int nblocks, const float* dC, int64_t lddc,
   for (int b = 0; b < nblocks; ++b)
     vec = vec && aligned16(W[b]) && (ldw[b] % 4) == 0 && (kb[b] % 4) == 0;
   hipStream_t s = as_stream(stream);
+  if (gemm_precision() == HLHGAT_GEMM_BF16 &&
+      gemm_bf16_route(bf16_grad_ok(dC, lddc, nblocks, W, ldw, kb, N)))
+    return launch_proj_bwd_data_bf16(&a, tnd, s);
   if (vec && big_data_ok(M, N, ktot)) {
     int cfg;
     const int64_t nblk = data_big_setup(a, cfg);
@@ -1421,8 +1409,11 @@ extern "C" int hlhgat_proj_bwd_weight(int nblocks, const float* dC, int64_t lddc
     vec = vec && A[b] && aligned16(A[b]) && (lda[b] % 4) == 0 && (kb[b] % 4) == 0;
     ktot_w += kb[b];
   }
+  // booked once per launching call (M == 0 launches nothing)
+  const bool bf16 = M > 0 && gemm_precision() == HLHGAT_GEMM_BF16 &&
+                    gemm_bf16_route(bf16_grad_ok(dC, lddc, nblocks, A, lda, kb, N));
   WeightPlan p = plan_weight(nblocks, kb, M, N, dbias != nullptr,
-                             vec && big_weight_ok(M, N, ktot_w));
+                             !bf16 && vec && big_weight_ok(M, N, ktot_w));
   HLH_CHECK_ARG(workspace && workspace_floats >= (int64_t)p.splits * p.part_stride,
                 "proj_bwd_weight: workspace too small");
   BwdWeightArgs a{};
@@ -1468,7 +1459,10 @@ extern "C" int hlhgat_proj_bwd_weight(int nblocks, const float* dC, int64_t lddc
     return HLHGAT_OK;
   }
   dim3 grid(1, (unsigned)p.tiles_total, (unsigned)p.splits);
-  if (p.big)
+  if (bf16) {
+    const int rc = launch_proj_bwd_weight_bf16(&a, p.tiles_total, p.splits, s);
+    if (rc != HLHGAT_OK) return rc;
+  } else if (p.big)
     launch_weight_big(p.big, (unsigned)(p.tiles_total * p.splits), s, nullptr, a);
   else if (vec)
     launch(k_proj_bwd_weight32, dim3(grid), dim3(256), 0, s, nullptr, a);
@@ -1646,6 +1640,12 @@ int proj_bwd_impl(int64_t M, int64_t N, const float* dC, int64_t lddc, int nb_w,
     for (int b = 0; b < nb_w && fuse; ++b) fuse = vec_ok(A[b], lda[b], kb_w[b]);
   }
   for (int b = 0; b < nb_d && fuse; ++b) fuse = vec_ok(W[b], ldw[b], kb_d[b]);
+  // bf16 mode: a side the bf16 kernels take goes through the separate calls
+  // below (each books and dispatches itself); nothing is deferred
+  if (fuse && gemm_precision() == HLHGAT_GEMM_BF16 &&
+      ((want_w && bf16_grad_ok(dC, lddc, nb_w, A, lda, kb_w, N)) ||
+       (want_d && bf16_grad_ok(dC, lddc, nb_d, W, ldw, kb_d, N))))
+    fuse = false;
   if (prev && !fuse) {  // run the merged reduction on its own first
     const int rc = run_reduce(*prev, as_stream(stream));
     if (rc != HLHGAT_OK) return rc;

@@ -26,5 +26,7 @@ from .metrics import (AccuracyMeter, Collector, F1Meter, RegressionMeter,  # noq
 from .nn import (BatchNorm, CrossEntropyLoss, FocalLoss, Linear,  # noqa: F401,E402
                  MaskedBCEWithLogitsLoss, MSELoss, Sequential, SimplexDropout,
                  global_mean_pool)
+from .precision import (gemm_bf16_eligible, gemm_precision_stats,  # noqa: F401,E402
+                        get_matmul_precision, matmul_precision, set_matmul_precision)
 
 __version__ = "0.1.0"

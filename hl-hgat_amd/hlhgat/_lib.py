@@ -100,6 +100,10 @@ SIGNATURES = {
     "hlhgat_set_proj_bn_split": (c_i32, [c_i32]),
     "hlhgat_set_proj_bwd_rows": (c_i32, [c_i32]),
     "hlhgat_set_gemm_big": (c_i32, [c_i32, c_i64]),
+    "hlhgat_set_gemm_precision": (c_i32, [c_i32]),
+    "hlhgat_get_gemm_precision": (c_i32, []),
+    "hlhgat_gemm_bf16_eligible": (c_i32, [c_i32, P_i64, P_i64, c_i64, c_i32]),
+    "hlhgat_gemm_precision_stats": (c_i32, [P_i64, c_i32]),
     "hlhgat_proj_bn_fused_capacity": (c_i32, [P_i64]),
     "hlhgat_set_bn_one_launch": (c_i32, [c_i32]),
     "hlhgat_get_bn_one_launch": (c_i32, []),

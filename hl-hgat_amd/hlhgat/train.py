@@ -34,7 +34,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import ops, precision
 from .distributed import collectives_on
 from .nn import SimplexDropout
 
@@ -285,6 +285,13 @@ class TrainStep:
     with, and ``set_lr`` raises there when graphs are on.  Betas, eps and
     weight decay are host constants fixed at construction.
 
+    Matmul precision.  ``matmul_precision`` ("fp32" | "bf16" | None = the
+    global hlhgat.get_matmul_precision() at construction) is fixed for the
+    object's life and set around every call -- eager step, capture and replay
+    -- then restored, so a cached graph never meets the other mode.  Master
+    weights, gradients and Adam state are fp32 either way; checkpoints do not
+    record the mode.
+
     Resume.  ``state_dict()`` / ``load_state_dict()`` carry the model, the
     optimiser (moments, step count, learning rate) and the HIP dropout
     counter; loading writes into the existing buffers, so captured graphs
@@ -293,7 +300,12 @@ class TrainStep:
     def __init__(self, model: torch.nn.Module, loss_fn: Callable, lr: float = 1e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  graphs: bool = True, max_graphs: int = 32, stage_slots: int = STAGE_SLOTS,
-                 overlap: Optional[bool] = None, bucket_mb: Optional[float] = None):
+                 overlap: Optional[bool] = None, bucket_mb: Optional[float] = None,
+                 matmul_precision: Optional[str] = None):
+        # fixed for the object's life (None: the global value now) and set
+        # around every call, so a cached graph never replays beside eager
+        # steps or captures of the other mode
+        self.matmul_precision = precision.resolve(matmul_precision)
         if isinstance(model, torch.nn.parallel.DistributedDataParallel):
             # DDP would all-reduce the gradients in its hooks and TrainStep again in
             # its bucket (two reductions, and DDP's gradient_as_bucket_view fights the
@@ -926,6 +938,10 @@ class TrainStep:
                 self._outstanding -= 1
 
     def __call__(self, batch) -> torch.Tensor:
+        with precision.matmul_precision(self.matmul_precision):
+            return self._step(batch)
+
+    def _step(self, batch) -> torch.Tensor:
         # a kernel of an earlier step that reported unusable results (the
         # device error word, read without synchronising) stops training here
         if self._ext is not None:
@@ -1072,9 +1088,10 @@ class InferStep:
     launches of the forward."""
 
     def __init__(self, model: torch.nn.Module, graphs: bool = True, max_graphs: int = 32,
-                 meter: Optional[Callable] = None):
+                 meter: Optional[Callable] = None, matmul_precision: Optional[str] = None):
         self.model = model
         self.meter = meter
+        self.matmul_precision = precision.resolve(matmul_precision)  # as TrainStep's
         params = list(model.parameters())
         dev = params[0].device if params else torch.device("cpu")
         self.device = dev
@@ -1127,6 +1144,10 @@ class InferStep:
         return ent
 
     def __call__(self, batch):
+        with precision.matmul_precision(self.matmul_precision):
+            return self._step(batch)
+
+    def _step(self, batch):
         if ops._ext is not None and self.device.type == "cuda":  # a CPU model launches nothing
             ops.check_device_errors(sync=False)
         if not self.graphs:

@@ -761,6 +761,40 @@ int hlhgat_proj_bn_fwd(int nblocks, const float* const* A, const int64_t* lda,
  * shape.  Env HLHGAT_GEMM_BIG sets the initial mode.  min_m <= 0 keeps the
  * current threshold. */
 int hlhgat_set_gemm_big(int mode, int64_t min_m);
+/* Matmul precision of the projections, process-wide like hlhgat_set_gemm_big.
+ * HLHGAT_GEMM_FP32 (the default): the fp32 MFMA kernels, bit for bit as
+ * without this switch.  HLHGAT_GEMM_BF16: hlhgat_proj_fwd, hlhgat_proj_bwd_data
+ * and hlhgat_proj_bwd_weight run kernels that round their two operands to bf16
+ * (round to nearest even) on load and accumulate the exact products in fp32
+ * (v_mfma_f32_16x16x32_bf16): forward rounds A and W, the data gradient dC and
+ * W, the weight gradient dC and A.  Storage, bias, accumulate adds, the bias
+ * gradient (summed from the unrounded dC) and the deterministic split
+ * reduction stay fp32; the summation order is unspecified but fixed: two runs
+ * are bitwise equal.  The mode is read when a GEMM is launched (forward and
+ * backward alike), so a captured graph keeps the mode it was captured in.
+ * In bf16 mode an eligible hlhgat_proj_bn_fwd runs the bf16 projection and
+ * then the fp32 BatchNorm kernels, and hlhgat_proj_bwd / hlhgat_proj_bwd_defer
+ * with an eligible side run the two separate calls (a merge descriptor is
+ * reduced first, nothing is deferred: *deferred = 0).  The temporal
+ * convolution front end (hlhgat_tconv_*) is fp32 in either mode. */
+#define HLHGAT_GEMM_FP32 0
+#define HLHGAT_GEMM_BF16 1
+int hlhgat_set_gemm_precision(int mode);
+int hlhgat_get_gemm_precision(void);
+/* 1 if a GEMM call with these reduction widths takes the bf16 kernels in bf16
+ * mode, else 0 (it runs the fp32 kernels, e.g. the 18-wide input projection or
+ * an N = 1 head).  The rule: 1 <= nblocks <= HLHGAT_MAX_BLOCKS; every
+ * kb[b] > 0 and kb[b] % 8 == 0; every row stride ld[b] >= kb[b] and
+ * ld[b] % 4 == 0 (ld may be NULL: not checked); N > 0 and N % 4 == 0;
+ * aligned16 != 0, i.e. every operand pointer of the call (the blocks and,
+ * for the gradients, dC) is 16-byte aligned.  The gradients also need
+ * lddc % 4 == 0.  The outputs need no alignment. */
+int hlhgat_gemm_bf16_eligible(int nblocks, const int64_t* kb, const int64_t* ld, int64_t N,
+                              int aligned16);
+/* Host-side counters of GEMM calls made in bf16 mode: out[0] = calls sent to
+ * the bf16 kernels, out[1] = calls that fell back to the fp32 kernels
+ * (ineligible).  reset != 0 zeroes them after reading. */
+int hlhgat_gemm_precision_stats(int64_t out[2], int reset);
 /* 0: the fused Linear backward (hlhgat_proj_bwd / _defer) uses one
  * data-gradient workgroup per (row block, 64-column tile) instead of one per
  * row block covering every column tile (N <= 64); bitwise the same (tests). */
