@@ -24,7 +24,7 @@ from . import metrics  # noqa: F401,E402
 from .metrics import (AccuracyMeter, Collector, F1Meter, RegressionMeter,  # noqa: F401,E402
                       eval_ap)
 from .nn import (BatchNorm, CrossEntropyLoss, FocalLoss, Linear,  # noqa: F401,E402
-                 MaskedBCEWithLogitsLoss, MSELoss, Sequential, SimplexDropout,
+                 MaskedBCEWithLogitsLoss, MSELoss, PESignFlip, Sequential, SimplexDropout,
                  global_mean_pool)
 from .precision import (gemm_bf16_eligible, gemm_precision_stats,  # noqa: F401,E402
                         get_matmul_precision, matmul_precision, set_matmul_precision)

@@ -142,6 +142,8 @@ SIGNATURES = {
                                     C.c_uint32, C.c_uint32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "hlhgat_mask_csr_values": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "hlhgat_mask_hodge_factor": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hlhgat_pe_flip": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "hlhgat_pe_signs": (c_i32, [c_i64, c_i64, C.c_uint32, c_vp, c_vp, c_vp]),
     "hlhgat_edge_absdiff":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                                     c_vp]),
     "hlhgat_pool_mean_bwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
@@ -272,6 +274,13 @@ class HodgeFactorDesc(C.Structure):
     _fields_ = [("node_rowptr", c_vp), ("node_edge", c_vp), ("node_sign", c_vp),
                 ("node_order", c_vp), ("n_nodes", c_i64), ("ends", c_vp), ("alpha", c_vp),
                 ("edge_order", c_vp), ("n_edges", c_i64)]
+
+
+class PeSideDesc(C.Structure):
+    """hlhgat_pe_side_t (include/hlhgat.h)."""
+    _fields_ = [("x", c_vp), ("ldx", c_i64), ("y", c_vp), ("ldy", c_i64), ("seg_ptr", c_vp),
+                ("n_graphs", c_i64), ("n_rows", c_i64), ("n_fixed", c_i32), ("n_flip", c_i32),
+                ("site", C.c_uint32)]
 
 
 class PackedGraphsDesc(C.Structure):

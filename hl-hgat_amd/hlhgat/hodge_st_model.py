@@ -121,10 +121,16 @@ class _PyrHead(nn.Module):
                 nn.Dropout(dropout_ratio_mlp)))
             mlp_insize = mlp_outsize
         self.out = Linear(mlp_insize, num_classes)
+        # the training set's PE sign-flip augmentation (the stored datasets'
+        # get(), lib/Hodge_Dataset.py:425-440) as a submodule: an nn.PESignFlip,
+        # or None (the stored signs); no state_dict keys
+        self.register_module("pe_flip", None)
 
     def forward(self, data, device="cuda:0", if_final_layer=False):
         x_s, edge_index_s, edge_weight_s = data.x_s, data.edge_index_s, data.edge_weight_s
         x_t, edge_index_t, edge_weight_t = data.x_t, data.edge_index_t, data.edge_weight_t
+        if self.pe_flip is not None:  # training: fresh PE signs, out of place; eval: as stored
+            x_t, x_s = self.pe_flip(x_t, x_s, data)
         # the dense concatenations x_t0 / x_s0 (:631-632) live in one slab per
         # side; every block's conv writes its output into its column block
         width = self.initial_channel + sum(c * f for c, f in zip(self.channels, self.filters))
@@ -290,10 +296,16 @@ class HL_HGCNN_zinc_dense_poolint3_pyr(nn.Module):
                 nn.Dropout(dropout_ratio_mlp)))
             mlp_insize = mlp_outsize
         self.out = Linear(mlp_insize, num_classes)
+        # the training set's PE sign-flip augmentation (the stored datasets'
+        # get(), lib/Hodge_Dataset.py:425-440) as a submodule: an nn.PESignFlip,
+        # or None (the stored signs); no state_dict keys
+        self.register_module("pe_flip", None)
 
     def forward(self, data, device="cuda:0"):
         x_s, edge_index_s, edge_weight_s = data.x_s, data.edge_index_s, data.edge_weight_s
         x_t, edge_index_t, edge_weight_t = data.x_t, data.edge_index_t, data.edge_weight_t
+        if self.pe_flip is not None:  # training: fresh PE signs, out of place; eval: as stored
+            x_t, x_s = self.pe_flip(x_t, x_s, data)
         width = self.initial_channel + sum((c + 1) * f for c, f in zip(self.channels, self.filters))
         dense = x_t.is_cuda and x_t.dim() == 2 and ops.DENSE_SLAB
         if dense:
@@ -584,6 +596,10 @@ class _AttPoolHead(nn.Module):
                 nn.Dropout(dropout_ratio_mlp)))
             mlp_insize = mlp_outsize
         self.out = Linear(mlp_insize, num_classes)
+        # the training set's PE sign-flip augmentation (the stored datasets'
+        # get(), lib/Hodge_Dataset.py:425-440) as a submodule: an nn.PESignFlip,
+        # or None (the stored signs); no state_dict keys
+        self.register_module("pe_flip", None)
 
     def _slab_ends(self, i: int) -> bool:
         """Level i ends by scaling (att) or pooling x0: the next level starts
@@ -613,6 +629,10 @@ class _AttPoolHead(nn.Module):
                                                      d0.x_s.size(0))
         x_s, edge_index_s, edge_weight_s = d0.x_s[:, 1:], d0.edge_index_s, d0.edge_weight_s
         x_t, edge_index_t, edge_weight_t = d0.x_t[:, 1:], d0.edge_index_t, d0.edge_weight_t
+        if self.pe_flip is not None:
+            # on the feature views: column 0 is the cluster index, not a feature
+            # (the reference's ones(node_dim + 1)); training only, out of place
+            x_t, x_s = self.pe_flip(x_t, x_s, d0)
         x_t, x_s = self.HL_init_conv(x_t, edge_index_t, edge_weight_t, x_s, edge_index_s,
                                      edge_weight_s)
         x_t0, x_s0 = x_t, x_s

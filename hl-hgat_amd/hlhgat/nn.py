@@ -18,7 +18,7 @@ import torch.nn as tnn
 
 __all__ = ["Sequential", "BatchNorm", "Linear", "L1Loss", "MSELoss", "BCEWithLogitsLoss",
            "FocalLoss", "MaskedBCEWithLogitsLoss", "CrossEntropyLoss", "glorot",
-           "global_mean_pool", "SimplexDropout"]
+           "global_mean_pool", "SimplexDropout", "PESignFlip"]
 
 
 def glorot(t: torch.Tensor) -> None:
@@ -649,3 +649,80 @@ class SimplexDropout(tnn.Module):
         ops.set_row_mask(ei, own)
         ops.refresh_row_mask(ei, w, n)
         return batch
+
+
+class PESignFlip(tnn.Module):
+    """The sign-flip augmentation of the eigenvector positional encoding, on
+    the device and under graph replay.  Every stored dataset of the reference
+    multiplies the PE columns of x_t and of x_s by fresh random signs in
+    ``get()``, per sample and per access (lib/Hodge_Dataset.py:425-440 ZINC,
+    :554-569 and :635-650 peptides, :869-881 CIFAR10SP: ``x[:, :dim] *
+    cat([ones(n_fixed), -1 + 2 * randint(0, 2, (keig,))])``).
+
+    ``forward(x_t, x_s, batch)`` returns the flipped ``(y_t, y_s)`` of widths
+    ``node_dim + keig`` and ``edge_dim + keig`` (the head constructors'
+    arguments; ``keig=None`` keeps every stored column): one launch for both
+    sides (ops.pe_flip), out of place, so the caller's batch is never
+    modified.  One sign per (graph, side, PE column), read off
+    ``batch.seg_ptr_t`` / ``batch.seg_ptr_s``; padding rows of a static-shape
+    batch are copied.  The draw is counter-based on the dropout state shared
+    with the feature Dropout and SimplexDropout, so TrainStep's one advance
+    per step serves all three and a captured step draws fresh signs on every
+    replay.  ``site`` is the module's ordinal k: modules with different k draw
+    independent signs.  The heads that take PE columns carry a ``pe_flip``
+    slot (None by default) and apply the module to their feature views first
+    thing in ``forward``.
+
+    In eval mode the inputs are returned as they are and nothing is launched.
+    The reference's validation and test sets flip too (they run the same
+    ``get()``), but eigenvector signs are arbitrary: the stored signs are as
+    valid a draw as any, and evaluation stays deterministic.  No parameters,
+    no buffers, no state_dict keys; CPU tensors raise in training mode (no
+    CPU path)."""
+
+    def __init__(self, node_dim: int, edge_dim: int, keig: Union[int, None] = None,
+                 site: int = 0):
+        super().__init__()
+        from .ops import PE_MAX_WIDTH, PE_SITES
+        for name, v in (("node_dim", node_dim), ("edge_dim", edge_dim)):
+            if not 0 <= int(v) <= PE_MAX_WIDTH:
+                raise ValueError(f"PESignFlip: {name} {v} out of range")
+        if keig is not None and not (0 <= int(keig) and int(keig) + max(int(node_dim), int(edge_dim))
+                                     <= PE_MAX_WIDTH):
+            raise ValueError(f"PESignFlip: keig {keig} out of range")
+        if not 0 <= int(site) < PE_SITES:
+            raise ValueError(f"PESignFlip: site {site} out of range")
+        self.node_dim, self.edge_dim = int(node_dim), int(edge_dim)
+        self.keig = None if keig is None else int(keig)
+        self.site = int(site)
+
+    def extra_repr(self) -> str:
+        return (f"node_dim={self.node_dim}, edge_dim={self.edge_dim}, keig={self.keig}, "
+                f"site={self.site}")
+
+    def widths(self, x_t: torch.Tensor, x_s: torch.Tensor) -> Tuple[int, int]:
+        """(PE columns flipped on x_t, on x_s)."""
+        out = []
+        for s, x, fixed in (("t", x_t, self.node_dim), ("s", x_s, self.edge_dim)):
+            k = x.size(1) - fixed if self.keig is None else self.keig
+            if x.dim() != 2 or k < 0 or x.size(1) < fixed + k:
+                raise RuntimeError(f"PESignFlip: x_{s} {tuple(x.shape)} has fewer than {fixed} + "
+                                   f"{max(k, 0)} columns (the packers fix the PE width when a "
+                                   f"dataset is built)")
+            out.append(k)
+        return out[0], out[1]
+
+    def forward(self, x_t: torch.Tensor, x_s: torch.Tensor, batch):
+        if not self.training:
+            return x_t, x_s
+        from . import ops
+        if not (x_t.is_cuda and x_s.is_cuda):
+            raise RuntimeError("PESignFlip: the batch must be on a ROCm device (got "
+                               f"{x_t.device}); the HIP path has no CPU fallback")
+        seg_t, seg_s = getattr(batch, "seg_ptr_t", None), getattr(batch, "seg_ptr_s", None)
+        if not (torch.is_tensor(seg_t) and torch.is_tensor(seg_s)):
+            raise RuntimeError("PESignFlip: the batch has no seg_ptr_t / seg_ptr_s (hodge_dataset."
+                               "collate builds them from the per-graph row counts)")
+        k_t, k_s = self.widths(x_t, x_s)
+        return ops.pe_flip(x_t, seg_t, self.node_dim, k_t, x_s, seg_s, self.edge_dim, k_s,
+                           site=self.site)

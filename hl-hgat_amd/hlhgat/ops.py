@@ -33,6 +33,7 @@ __all__ = [
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
+    "pe_flip", "pe_signs",
     "bce_logits_loss", "cross_entropy", "mse_loss", "average_precision",
     "collect_rows", "f1_per_graph", "argmax_correct", "regression_summary",
     "fc_prepare", "fc_dense", "fc_edges", "fc_pair_table", "FcPrepared", "mlgc_device",
@@ -1965,6 +1966,157 @@ def dropout(x: torch.Tensor, p: float, training: bool = True,
     st = _dropout_st(x.device)
     y = _ext.dropout(x2, T, s, st.dev, st.next_site(), out)  # C++ autograd node
     return y if x.dim() == 2 else y.view(shape)
+
+
+# ----------------------------------------------------------------------------
+# PE sign-flip augmentation (counter-based Philox signs, csrc/peflip.hip)
+# ----------------------------------------------------------------------------
+PE_SITES = 1 << 29  # module ordinals k; the kernel's site word is 2k + side (side 0 = t, 1 = s)
+PE_MAX_WIDTH = 65536  # n_fixed + n_flip
+
+
+def _pe_site(site: int, side: int) -> int:
+    if not 0 <= int(site) < PE_SITES:
+        raise ValueError(f"pe_flip: site {site} out of range (0 <= site < 2^29)")
+    if side not in (0, 1):
+        raise ValueError(f"pe_flip: side must be 0 (t) or 1 (s), got {side!r}")
+    return 2 * int(site) + side
+
+
+def _pe_widths(n_fixed: int, n_flip: int, name: str) -> Tuple[int, int]:
+    n_fixed, n_flip = int(n_fixed), int(n_flip)
+    if n_fixed < 0 or n_flip < 0 or n_fixed + n_flip > PE_MAX_WIDTH:
+        raise ValueError(f"pe_flip: {name}: n_fixed = {n_fixed}, n_flip = {n_flip} (both >= 0, "
+                         f"n_fixed + n_flip <= {PE_MAX_WIDTH})")
+    return n_fixed, n_flip
+
+
+def _pe_desc(src, dst, seg, n_fixed, n_flip, site) -> "_lib.PeSideDesc":
+    return _lib.PeSideDesc(src.data_ptr(), _ld(src), dst.data_ptr(), _ld(dst), _ptr(seg),
+                           0 if seg is None else seg.numel() - 1, src.size(0), n_fixed, n_flip,
+                           site)
+
+
+def _pe_launch(descs, state: torch.Tensor, snap: torch.Tensor, ref: torch.Tensor) -> None:
+    arr = (_lib.PeSideDesc * len(descs))(*descs)
+    check(LIB.hlhgat_pe_flip(C.cast(arr, C.c_void_p), len(descs), state.data_ptr(),
+                             snap.data_ptr(), _stream(ref)), "pe_flip")
+
+
+class _PEFlipFn(torch.autograd.Function):
+    """Both sides in one launch each way; the backward is the forward's entry
+    point on dy at the forward's {seed, step} snapshot (no sign table stored)."""
+
+    @staticmethod
+    def forward(ctx, x_t, x_s, seg_t, seg_s, meta, state):
+        xs, segs = (x_t, x_s), (seg_t, seg_s)
+        ref = x_t if x_t is not None else x_s
+        ys, descs = [None, None], []
+        for i, x in enumerate(xs):
+            if x is None:
+                continue
+            n_fixed, n_flip, site = meta[i]
+            ys[i] = torch.empty(x.size(0), n_fixed + n_flip, device=x.device, dtype=x.dtype)
+            descs.append(_pe_desc(x, ys[i], segs[i], n_fixed, n_flip, site))
+        snap = torch.empty(2, dtype=torch.int64, device=ref.device)
+        _pe_launch(descs, state, snap, ref)
+        ctx.meta = meta
+        ctx.widths = tuple(None if x is None else x.size(1) for x in xs)
+        ctx.save_for_backward(snap, seg_t, seg_s)
+        return ys[0], ys[1]
+
+    @staticmethod
+    def backward(ctx, g_t, g_s):
+        snap, seg_t, seg_s = ctx.saved_tensors
+        segs = (seg_t, seg_s)
+        dxs, descs, ref = [None, None], [], None
+        for i, g in enumerate((g_t, g_s)):
+            if g is None or not ctx.needs_input_grad[i]:
+                continue
+            n_fixed, n_flip, site = ctx.meta[i]
+            g = _rows2d(g, "grad")
+            w = n_fixed + n_flip
+            if ctx.widths[i] == w:
+                dxs[i] = dst = torch.empty(g.size(0), w, device=g.device, dtype=g.dtype)
+            else:  # the columns the forward dropped get no gradient
+                dxs[i] = torch.zeros(g.size(0), ctx.widths[i], device=g.device, dtype=g.dtype)
+                dst = dxs[i][:, :w]
+            descs.append(_pe_desc(g, dst, segs[i], n_fixed, n_flip, site))
+            ref = g
+        if descs:
+            _pe_launch(descs, snap, snap, ref)
+        return dxs[0], dxs[1], None, None, None, None
+
+
+def pe_signs(seg_ptr_or_n_graphs, n_flip: int, site: int = 0, side: int = 0,
+             device=None) -> torch.Tensor:
+    """The [n_graphs, n_flip] table of +1.0 / -1.0 that pe_flip multiplies the
+    flipped columns of side `side` (0 = t, 1 = s) of module ordinal `site` by
+    at the current dropout state (dropout_state) -- for tests and for logging
+    the draw.  The first argument is a seg_ptr tensor ([n_graphs + 1], its
+    device is used) or the number of graphs.  One launch; advances nothing."""
+    if torch.is_tensor(seg_ptr_or_n_graphs):
+        if seg_ptr_or_n_graphs.dim() != 1 or seg_ptr_or_n_graphs.numel() < 1:
+            raise RuntimeError("hlhgat: pe_signs: seg_ptr must be a [n_graphs + 1] tensor")
+        G = seg_ptr_or_n_graphs.numel() - 1
+        device = seg_ptr_or_n_graphs.device if device is None else device
+    else:
+        G = int(seg_ptr_or_n_graphs)
+    _, n_flip = _pe_widths(0, n_flip, "pe_signs")
+    if G < 0:
+        raise ValueError(f"pe_signs: n_graphs = {G}")
+    word = _pe_site(site, side)
+    st = _dropout_st(device)
+    out = torch.empty(G, n_flip, device=st.device, dtype=torch.float32)
+    check(LIB.hlhgat_pe_signs(G, n_flip, word, st.dev.data_ptr(), out.data_ptr(), _stream(out)),
+          "pe_signs")
+    return out
+
+
+def pe_flip(x_t: Optional[torch.Tensor], seg_t: Optional[torch.Tensor], fixed_t: int,
+            flip_t: int, x_s: Optional[torch.Tensor] = None,
+            seg_s: Optional[torch.Tensor] = None, fixed_s: int = 0, flip_s: int = 0,
+            site: int = 0) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The sign flip of the eigenvector positional-encoding columns that the
+    reference's stored datasets apply per sample in get()
+    (lib/Hodge_Dataset.py:425-440: ``x[:, :n_fixed + n_flip] * cat([ones(
+    n_fixed), -1 + 2 * randint(0, 2, (n_flip,))])``, one draw for x_t and one
+    for x_s) for every graph of a batch: y = (y_t, y_s), both sides in ONE
+    launch, out of place (the caller's batch is never modified).  x_<side> is
+    [n_rows, >= fixed + flip] fp32 with unit inner stride (a column window
+    such as x[:, 1:] is read in place; wider inputs are truncated);
+    seg_<side> is the int32 [n_graphs + 1] row pointer of the batch
+    (batch.seg_ptr_<side>); rows at or beyond seg[-1] (static-shape padding)
+    are copied unflipped.  Either side may be None.  The signs are a function
+    of (seed, step, site, side, graph, column) on the shared dropout state
+    (dropout_state; csrc/peflip.hip), so a captured launch draws fresh signs
+    on every replay; ops.pe_signs returns them.  Differentiable: the backward
+    is the same launch on dy at the forward's {seed, step} snapshot.  CPU
+    tensors raise (no CPU path)."""
+    word_t, word_s = _pe_site(site, 0), _pe_site(site, 1)
+    xs, segs, meta = [None, None], [None, None], [None, None]
+    for i, (x, seg, nf, nl, word, nm) in enumerate((
+            (x_t, seg_t, fixed_t, flip_t, word_t, "t"), (x_s, seg_s, fixed_s, flip_s, word_s, "s"))):
+        if x is None:
+            continue
+        _req_dev(x, "x_" + nm)
+        nf, nl = _pe_widths(nf, nl, "x_" + nm)
+        if x.dim() != 2 or x.size(1) < nf + nl:
+            raise RuntimeError(f"hlhgat: pe_flip: x_{nm} {tuple(x.shape)} has fewer than "
+                               f"{nf} + {nl} columns")
+        if seg is None:
+            raise RuntimeError(f"hlhgat: pe_flip: x_{nm} needs its seg_ptr (int32 [n_graphs + 1])")
+        _req_dev(seg, "seg_" + nm, torch.int32)
+        if seg.dim() != 1 or seg.numel() < 1 or not seg.is_contiguous() or seg.device != x.device:
+            raise RuntimeError(f"hlhgat: pe_flip: seg_{nm} must be a contiguous [n_graphs + 1] "
+                               f"tensor on x_{nm}'s device")
+        xs[i], segs[i], meta[i] = _rows2d(x, "x_" + nm), seg, (nf, nl, word)
+    if xs[0] is None and xs[1] is None:
+        return None, None
+    if xs[0] is not None and xs[1] is not None and xs[0].device != xs[1].device:
+        raise RuntimeError("hlhgat: pe_flip: x_t and x_s must be on one device")
+    st = _dropout_st((xs[0] if xs[0] is not None else xs[1]).device)
+    return _PEFlipFn.apply(xs[0], xs[1], segs[0], segs[1], tuple(meta), st.dev)
 
 
 def att_score(Qc, Qs, Kr, w_cross: float, w_self: float, sqrt_dk: float,

@@ -36,7 +36,7 @@ import torch.distributed as dist
 
 from . import ops, precision
 from .distributed import collectives_on
-from .nn import SimplexDropout
+from .nn import PESignFlip, SimplexDropout
 
 __all__ = ["Staged", "TrainStep", "InferStep", "batch_key", "forward_collectives"]
 
@@ -402,7 +402,10 @@ class TrainStep:
         # advance per step, the rank seeds and the checkpointed counter serve both
         self._simplex = [m for m in model.modules() if isinstance(m, SimplexDropout)] \
             if dev.type == "cuda" else []
-        if self._dropouts or self._simplex:
+        # the PE sign flip (nn.PESignFlip) likewise: fresh signs on every replay
+        self._pe_flips = [m for m in model.modules() if isinstance(m, PESignFlip)] \
+            if dev.type == "cuda" else []
+        if self._dropouts or self._simplex or self._pe_flips:
             if self.world > 1:
                 ops.dropout_set_rank(dist.get_rank(), dev)
             else:
@@ -421,11 +424,12 @@ class TrainStep:
         """Start of a step: zero the gradient bucket.  With the HIP Adam the
         step count is incremented in the same launch (hlhgat_adam_prepare);
         returns whether it was (the update then must not count again).  A
-        model with a live Dropout or SimplexDropout also advances the dropout
-        step here (one more launch for both kinds; captured, they draw fresh
-        masks on every replay)."""
+        model with a live Dropout, SimplexDropout or PESignFlip also advances
+        the dropout step here (one more launch for all kinds; captured, they
+        draw fresh masks and signs on every replay)."""
         if (self._dropouts and ops.HIP_DROPOUT and any(m.training for m in self._dropouts)) \
-                or any(m.training for m in self._simplex):
+                or any(m.training for m in self._simplex) \
+                or any(m.training for m in self._pe_flips):
             ops.dropout_advance(self.device)
         if self._hip_adam:
             ops.adam_prepare(self.flat_grad, self.opt.state[self.master]["step"])
@@ -1000,14 +1004,15 @@ class TrainStep:
     # -- checkpoints --------------------------------------------------------
     def state_dict(self):
         """{"model", "opt"} (+ "dropout": (seed, step) and "dropout_site", the
-        host-side launch counter, when the model has a live HIP Dropout; eager
+        host-side launch counter, when the model has a live HIP Dropout, a
+        SimplexDropout or a PESignFlip; eager
         steps resume on the uninterrupted run's masks, a step captured after
         the resume draws equally valid masks at its own sites).  "opt" is the torch optimiser's state_dict: moments, step
         count and, with the HIP Adam, the fp64 tensor learning rate."""
         sd = {"model": self.model.state_dict(), "opt": self.opt.state_dict()}
         if self._hip_adam:  # a snapshot, not the live scalar later fills would change
             sd["opt"]["param_groups"][0]["lr"] = self._lr_dev.detach().clone()
-        if (self._dropouts and ops.HIP_DROPOUT) or self._simplex:
+        if (self._dropouts and ops.HIP_DROPOUT) or self._simplex or self._pe_flips:
             seed, step, site = ops.dropout_state(self.device)
             sd["dropout"] = (seed, step)
             sd["dropout_site"] = site
@@ -1060,7 +1065,7 @@ class TrainStep:
                 self._lr_dev.fill_(float(groups[0]["lr"]))
             if "initial_lr" in groups[0]:  # left by a scheduler; its own state is the caller's
                 self.opt.param_groups[0]["initial_lr"] = groups[0]["initial_lr"]
-        if "dropout" in sd and (self._dropouts or self._simplex):
+        if "dropout" in sd and (self._dropouts or self._simplex or self._pe_flips):
             seed, step = sd["dropout"]
             ops.dropout_set_state(seed, step, self.device, site=sd.get("dropout_site", 0))
 

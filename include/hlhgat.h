@@ -1397,6 +1397,56 @@ int hlhgat_mask_csr_values(const int32_t* rowptr, const int32_t* col, const floa
 int hlhgat_mask_hodge_factor(const hlhgat_hodge_factor_t* f, const float* mask, float* sign_out,
                              float* alpha_out, void* stream);
 
+/* ---- PE sign-flip augmentation ------------------------------------------ */
+/* The sign draw every stored dataset of the reference applies to the
+ * eigenvector positional-encoding columns in get(), per sample and per access
+ * (lib/Hodge_Dataset.py:425-440, :500-515, :554-569, :635-650, :869-881):
+ *   sign = cat([ones(n_fixed), -1 + 2 * randint(0, 2, (n_flip,))])
+ *   x = x[:, :n_fixed + n_flip] * sign
+ * Counter-based like hlhgat_dropout_fwd: state = {seed, step} (two int64,
+ * device) is read by the kernel, nothing is stored between steps.  Graph g,
+ * flipped column j (0-based among the flipped columns):
+ *   w    = word (j & 3) of philox4x32-10({g, 0x50450000 + (j >> 2), site,
+ *                                         step lo}, {seed lo, seed hi})
+ *   sign = (w >> 31) ? -1.0f : +1.0f
+ * site < 2^30; the callers use 2k + side (k: the module's ordinal, side 0 = t,
+ * 1 = s).  The second counter word lies above every value the feature dropout
+ * and the simplex dropout can put there (the high half of an element index
+ * >> 2, or 0), so the three draws never share a counter.
+ *
+ * One side of a flip: y[r][c] = x[r][c] for c < n_fixed and y[r][n_fixed + j]
+ * = x[r][n_fixed + j] * sign(g(r), j) for j < n_flip, r < n_rows, where g(r) is
+ * the graph with seg_ptr[g] <= r < seg_ptr[g + 1] (int32 [n_graphs + 1],
+ * ascending).  Rows in no graph (r >= seg_ptr[n_graphs], static-shape
+ * padding) are copied unflipped.  y is [n_rows, n_fixed + n_flip] at pitch
+ * ldy; x may be wider (the extra columns are dropped, as x[:, :node_dim]
+ * does) and may be a column window of a wider tensor (pitch ldx).  x and y
+ * never alias.  n_fixed + n_flip <= 65536. */
+typedef struct {
+  const float* x;
+  int64_t ldx;
+  float* y;
+  int64_t ldy;
+  const int32_t* seg_ptr;
+  int64_t n_graphs;
+  int64_t n_rows;
+  int32_t n_fixed;
+  int32_t n_flip;
+  uint32_t site;
+} hlhgat_pe_side_t;
+/* n_sides (1 or 2) sides in ONE launch, the grid partitioned between them.
+ * snap (two int64, device) receives the {seed, step} used; snap == state is
+ * allowed (a replay from a snapshot: the backward is this entry point on dy
+ * with the forward's snap as state).  A side with n_rows == 0 or n_fixed +
+ * n_flip == 0 moves nothing; when no side moves anything nothing is launched
+ * and snap is left alone.  n_flip == 0 is a copy. */
+int hlhgat_pe_flip(const hlhgat_pe_side_t* sides, int n_sides, const int64_t* state,
+                   int64_t* snap, void* stream);
+/* signs[g][j] (float [n_graphs, n_flip], contiguous) of the same draw at
+ * `site`: +1.0 or -1.0.  n_graphs == 0 or n_flip == 0 is a no-op. */
+int hlhgat_pe_signs(int64_t n_graphs, int64_t n_flip, uint32_t site, const int64_t* state,
+                    float* signs, void* stream);
+
 /* ---- brain input: z-scored series and functional connectivity ----------- */
 /* The per-sample arithmetic of Brain_MLGC_ALL.get (HL-HGAT-DEMO/lib/
  * Hodge_Dataset.py:130-145) and of the cohort loop that feeds FC2mask
