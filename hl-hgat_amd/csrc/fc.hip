@@ -54,14 +54,43 @@ __device__ __forceinline__ const float* fc_row(const float* x, int64_t ldx,
   return x + (r0 + i) * ldx + t0;
 }
 
+// Per-graph windows (hlhgat_fc_prepare_windows): graph g reads columns
+// [t0[g], t0[g] + len[g]) and everything it writes is padded to t_max columns.
+struct FcWindows {
+  const int32_t* t0;   // [G]
+  const int32_t* len;  // [G]
+  int64_t t_max;
+  unsigned* err;       // device error word (HLHGAT_DEVERR_TSERIES_LEN)
+};
+
+// the window of graph g, clamped to [2, t_max] samples inside the row
+__device__ __forceinline__ void fc_window(const FcWindows& w, int64_t g, int64_t ldx, int64_t& t0,
+                                          int64_t& T, bool report) {
+  const int64_t l = w.len[g], b = w.t0[g];
+  T = l < 2 ? 2 : (l > w.t_max ? w.t_max : l);
+  t0 = b < 0 ? 0 : (b > ldx - T ? ldx - T : b);
+  if (report && (T != l || t0 != b) && w.err) {
+    // host memory without PCIe atomics: load + store keeps the other bits
+    const unsigned old = __hip_atomic_load(w.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(w.err, old | (unsigned)HLHGAT_DEVERR_TSERIES_LEN, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_fc_rows(const float* __restrict__ x, int64_t ldx,
                                                  const int64_t* __restrict__ graph_rows,
                                                  int64_t G, int64_t N, int64_t t0, int64_t T,
                                                  float* __restrict__ zhat,
-                                                 double* __restrict__ stat) {
+                                                 double* __restrict__ stat, FcWindows w) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= G * N) return;  // whole waves leave: no barrier below
+  int64_t P = fc_pitch(T);
+  if constexpr (WIN) {
+    fc_window(w, row / N, ldx, t0, T, lane == 0 && row % N == 0);
+    P = fc_pitch(w.t_max);
+  }
   const float* xr = fc_row(x, ldx, graph_rows, row / N, N, row % N, t0);
   double s = 0.0;
   float lo = INFINITY, hi = -INFINITY;
@@ -91,7 +120,6 @@ __global__ __launch_bounds__(256) void k_fc_rows(const float* __restrict__ x, in
   }
   // a row constant over the window: 0 / 0 in exact arithmetic
   const double rn = (lo == hi) ? (double)NAN : 1.0 / sqrt(ss);
-  const int64_t P = fc_pitch(T);
   float* zr = zhat + row * P;
   for (int64_t t = lane; t < P; t += 64)
     zr[t] = t < T ? (float)(((double)xr[t] - mean) * rn) : 0.f;
@@ -110,13 +138,19 @@ __device__ __forceinline__ double block_sum_rows(int64_t N, double* red, F f) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_fc_z(const float* __restrict__ x, int64_t ldx,
                                               const int64_t* __restrict__ graph_rows, int64_t N,
                                               int64_t t0, int64_t T,
                                               const double* __restrict__ stat,
-                                              float* __restrict__ z) {
+                                              float* __restrict__ z, FcWindows w) {
   __shared__ double red[4];
   const int64_t g = blockIdx.y;
+  int64_t Tz = T;  // the row pitch of z
+  if constexpr (WIN) {
+    fc_window(w, g, ldx, t0, T, false);
+    Tz = w.t_max;
+  }
   const double* st = stat + 2 * g * N;
   const double cnt = (double)N * (double)T;
   const double mean = block_sum_rows(N, red, [&](int64_t i) { return st[2 * i]; }) / cnt;
@@ -128,10 +162,14 @@ __global__ __launch_bounds__(256) void k_fc_z(const float* __restrict__ x, int64
   const double sd = sqrt(ssq / (cnt - 1.0));  // unbiased, as torch.Tensor.std()
   const int64_t i0 = (int64_t)blockIdx.x * FC_ZROWS;
   const int64_t rows = N - i0 < FC_ZROWS ? N - i0 : FC_ZROWS;
-  for (int64_t e = threadIdx.x; e < rows * T; e += 256) {
-    const int64_t i = i0 + e / T, t = e % T;
+  for (int64_t e = threadIdx.x; e < rows * Tz; e += 256) {
+    const int64_t i = i0 + e / Tz, t = e % Tz;
+    if (WIN && t >= T) {  // past the graph's own window
+      z[(g * N + i) * Tz + t] = 0.f;
+      continue;
+    }
     const float v = fc_row(x, ldx, graph_rows, g, N, i, t0)[t];
-    z[(g * N + i) * T + t] = (float)(((double)v - mean) / sd);
+    z[(g * N + i) * Tz + t] = (float)(((double)v - mean) / sd);
   }
 }
 
@@ -230,9 +268,11 @@ extern "C" size_t hlhgat_fc_workspace_bytes(int64_t G, int64_t N, int64_t T) {
   return fc_zhat_bytes(G, N, T) + (size_t)(G * N) * 2 * sizeof(double);
 }
 
-extern "C" int hlhgat_fc_prepare(const float* x, int64_t ldx, const int64_t* graph_rows,
-                                 int64_t G, int64_t N, int64_t t0, int64_t T, float* z,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+// win NULL: one window (t0, T) for every graph; else per-graph windows padded
+// to T = win->t_max columns
+static int fc_prepare_impl(const float* x, int64_t ldx, const int64_t* graph_rows, int64_t G,
+                           int64_t N, int64_t t0, int64_t T, float* z, void* workspace,
+                           size_t workspace_bytes, const FcWindows* win, void* stream) {
   if (int rc = fc_check_ws(G == 0 ? nullptr : workspace, G, N, T, "fc_prepare")) return rc;
   HLH_CHECK_ARG(t0 >= 0, "fc_prepare: t0 = %lld < 0", (long long)t0);
   HLH_CHECK_ARG(t0 + T <= ldx, "fc_prepare: window t0 + T = %lld exceeds ldx = %lld",
@@ -245,15 +285,43 @@ extern "C" int hlhgat_fc_prepare(const float* x, int64_t ldx, const int64_t* gra
   hipStream_t s = as_stream(stream);
   float* zhat = static_cast<float*>(workspace);
   double* stat = reinterpret_cast<double*>(static_cast<char*>(workspace) + fc_zhat_bytes(G, N, T));
-  launch(k_fc_rows, dim3((unsigned)ceil_div(G * N, 4)), dim3(256), 0, s, nullptr, x, ldx,
-         graph_rows, G, N, t0, T, zhat, stat);
+  const dim3 grows((unsigned)ceil_div(G * N, 4));
+  const dim3 gz((unsigned)ceil_div(N, FC_ZROWS), (unsigned)G);
+  if (win)
+    launch(k_fc_rows<true>, grows, dim3(256), 0, s, nullptr, x, ldx, graph_rows, G, N, t0, T,
+           zhat, stat, *win);
+  else
+    launch(k_fc_rows<false>, grows, dim3(256), 0, s, nullptr, x, ldx, graph_rows, G, N, t0, T,
+           zhat, stat, FcWindows{});
   HLH_CHECK_LAUNCH();
   if (z) {
-    launch(k_fc_z, dim3((unsigned)ceil_div(N, FC_ZROWS), (unsigned)G), dim3(256), 0, s, nullptr,
-           x, ldx, graph_rows, N, t0, T, (const double*)stat, z);
+    if (win)
+      launch(k_fc_z<true>, gz, dim3(256), 0, s, nullptr, x, ldx, graph_rows, N, t0, T,
+             (const double*)stat, z, *win);
+    else
+      launch(k_fc_z<false>, gz, dim3(256), 0, s, nullptr, x, ldx, graph_rows, N, t0, T,
+             (const double*)stat, z, FcWindows{});
     HLH_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int hlhgat_fc_prepare(const float* x, int64_t ldx, const int64_t* graph_rows,
+                                 int64_t G, int64_t N, int64_t t0, int64_t T, float* z,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  return fc_prepare_impl(x, ldx, graph_rows, G, N, t0, T, z, workspace, workspace_bytes, nullptr,
+                         stream);
+}
+
+extern "C" int hlhgat_fc_prepare_windows(const float* x, int64_t ldx, const int64_t* graph_rows,
+                                         int64_t G, int64_t N, const int32_t* t0,
+                                         const int32_t* len, int64_t t_max, float* z,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  HLH_CHECK_ARG(G <= 0 || (t0 && len), "fc_prepare_windows: NULL window table");
+  HLH_CHECK_ARG(t_max >= 1, "fc_prepare_windows: t_max = %lld < 1", (long long)t_max);
+  const FcWindows win{t0, len, t_max, device_error_word()};
+  return fc_prepare_impl(x, ldx, graph_rows, G, N, 0, t_max, z, workspace, workspace_bytes, &win,
+                         stream);
 }
 
 extern "C" int hlhgat_fc_dense(const void* workspace, int64_t G, int64_t N, int64_t T, float* fc,

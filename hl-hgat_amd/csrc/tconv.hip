@@ -27,6 +27,20 @@ constexpr int WG_SUB = 64;    // rows per staging step of the weight gradient
 constexpr int WG_PITCH = 80;  // LDS row pitch there: rows q, q+1 on disjoint banks
 constexpr int WG_MAX = 512;   // row chunks (workgroups along the rows) at the most
 
+// Ragged time layout (hlhgat_tseries_map): series of different lengths stacked
+// compactly in a buffer of fixed capacity.  The position predicate of a row
+// then comes from a per-row (step, length) table instead of g % T, and the
+// rows from *n_rows on are dead: never read, written as zeros.
+struct RowTab {
+  const int2* tab;         // [capacity] (step within the series, series length)
+  const int32_t* n_rows;   // device scalar: the valid-row prefix
+};
+
+__device__ __forceinline__ int64_t live_rows(int64_t cap, const int32_t* n_rows) {
+  const int64_t v = (int64_t)*n_rows;
+  return v < cap ? (v < 0 ? 0 : v) : cap;
+}
+
 // ---------------------------------------------------------------------------
 // weight packing: the branches' nn.Conv1d weights [co_b][cin][taps_b] into one
 // [taps][Cout][cin] weight with structural zeros (forward), or its flipped
@@ -85,6 +99,7 @@ struct ConvArgs {
   float* y;
   int n1, n3;  // columns [0,n1): centre tap only; [n1,n1+n3): the centre three
   int vec_in, vec_out;
+  RowTab rt;  // ragged kernels only; M is then the capacity
 };
 
 template <bool VEC>
@@ -115,7 +130,16 @@ __device__ __forceinline__ void stage_rows(float (*lds)[KC], int nrows, const fl
   }
 }
 
-template <bool VEC>
+// rows [lo, hi) x columns [n_base, n_base + ncols) of y := 0 (the dead rows of
+// a ragged tile), by one wave
+__device__ __forceinline__ void zero_rows(float* y, int64_t ld, int64_t lo, int64_t hi,
+                                          int n_base, int ncols) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = lo; r < hi; ++r)
+    for (int c = lane; c < ncols; c += 64) y[r * ld + n_base + c] = 0.f;
+}
+
+template <bool VEC, bool RAG>
 __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) float xa[TM + 2 * HALO][KC];
   __shared__ __attribute__((aligned(16))) float wl[64][KC];
@@ -125,7 +149,21 @@ __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
   const int n_base = blockIdx.y * 64;
   const int half = a.taps >> 1;
   const int64_t g = row0 + wave * 16 + i;  // the row this lane feeds as A operand
-  const int tpos = g < a.M ? (int)(g % a.T) : -(1 << 20);
+  int64_t Mv = a.M;
+  int tpos, tlen = a.T;
+  if constexpr (RAG) {
+    Mv = live_rows(a.M, a.rt.n_rows);
+    const int64_t w0 = row0 + wave * 16;
+    if (row0 >= Mv) {  // a dead tile (the whole workgroup leaves)
+      zero_rows(a.y, a.cout, w0, min(w0 + 16, a.M), n_base, min(64, a.cout - n_base));
+      return;
+    }
+    const int2 e = g < Mv ? a.rt.tab[g] : make_int2(0, 0);
+    tpos = e.x;
+    tlen = e.y;
+  } else {
+    tpos = g < a.M ? (int)(g % a.T) : -(1 << 20);
+  }
 
   floatx4 acc[4];
 #pragma unroll
@@ -133,7 +171,7 @@ __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
 
   for (int c0 = 0; c0 < a.cin; c0 += KC) {
     __syncthreads();  // the previous chunk's readers are done with xa
-    stage_rows<VEC>(xa, TM + 2 * HALO, a.x, row0 - HALO, 0, a.M, a.cin, c0, a.cin);
+    stage_rows<VEC>(xa, TM + 2 * HALO, a.x, row0 - HALO, 0, Mv, a.cin, c0, a.cin);
     const int ns = min(4, (a.cin - c0 + 15) >> 4);
     for (int k = 0; k < a.taps; ++k) {
       __syncthreads();  // the previous tap's readers are done with wl
@@ -141,7 +179,7 @@ __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
                       a.cin);
       __syncthreads();
       const int d = k > half ? k - half : half - k;
-      const bool av = (unsigned)(tpos + k - half) < (unsigned)a.T;
+      const bool av = (unsigned)(tpos + k - half) < (unsigned)tlen;
       const int ar = wave * 16 + i + k - half + HALO;
       bool on[4];
 #pragma unroll
@@ -169,8 +207,12 @@ __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
   }
   __syncthreads();  // xa becomes the epilogue's transpose scratch
   float* scratch = &xa[0][0] + wave * (16 * (64 + 4));
-  store_tile_rows<4>(acc, scratch, row0 + wave * 16, a.M, a.y + n_base, a.cout,
+  store_tile_rows<4>(acc, scratch, row0 + wave * 16, Mv, a.y + n_base, a.cout,
                      a.cout - n_base, a.bias ? a.bias + n_base : nullptr, 0, a.vec_out != 0);
+  if constexpr (RAG) {
+    const int64_t w0 = row0 + wave * 16;
+    zero_rows(a.y, a.cout, max(w0, Mv), min(w0 + 16, a.M), n_base, min(64, a.cout - n_base));
+  }
 }
 
 // The Cin = 1 embedding (nn.Conv1d(1, C, taps, padding=taps/2), :483): VALU
@@ -180,11 +222,13 @@ __global__ __launch_bounds__(256) void k_tconv_fwd(ConvArgs a) {
 // module's [C][1][taps] layout.
 constexpr int EMB_R = 8;
 
-template <int V, typename IdxT>
+template <int V, typename IdxT, bool RAG>
 __global__ void k_tconv_embed_fwd(const float* __restrict__ x, int64_t M, int T,
                                   const float* __restrict__ w, const float* __restrict__ bias,
-                                  int C, int taps, float* __restrict__ y) {
+                                  int C, int taps, float* __restrict__ y, RowTab rt) {
   const int half = taps >> 1;
+  int64_t Mv = M;
+  if constexpr (RAG) Mv = live_rows(M, rt.n_rows);
   const IdxT cv = (IdxT)(C / V);
   const IdxT total = (IdxT)((M + EMB_R - 1) / EMB_R) * cv;
   for (IdxT j = (IdxT)blockIdx.x * blockDim.x + threadIdx.x; j < total;
@@ -199,12 +243,23 @@ __global__ void k_tconv_embed_fwd(const float* __restrict__ x, int64_t M, int T,
 #pragma unroll
       for (int k = 0; k < MAXTAPS; ++k) wr[u][k] = k < taps ? w[(c + u) * taps + k] : 0.f;
     }
-    int t = (int)(g0 % T);
+    int t = RAG ? 0 : (int)(g0 % T);
 #pragma unroll
     for (int r = 0; r < EMB_R; ++r) {
       const int64_t g = g0 + r;
       if (g < M) {
         typename VecT<V>::type v;
+        if constexpr (RAG) {
+          if (g >= Mv) {  // a dead row
+#pragma unroll
+            for (int u = 0; u < V; ++u) vget(v, u) = 0.f;
+            vstore<V>(y + g * C + c, v);
+            continue;
+          }
+          const int2 e = rt.tab[g];
+          t = e.x;
+          T = e.y;
+        }
 #pragma unroll
         for (int u = 0; u < V; ++u) vget(v, u) = bv[u];
         // every tap's load is issued unconditionally (clamped address, masked value)
@@ -219,7 +274,8 @@ __global__ void k_tconv_embed_fwd(const float* __restrict__ x, int64_t M, int T,
         }
         vstore<V>(y + g * C + c, v);
       }
-      if (++t == T) t = 0;
+      if constexpr (!RAG)
+        if (++t == T) t = 0;
     }
   }
 }
@@ -239,20 +295,25 @@ struct WgradArgs {
   int T, cin, cout, taps;
   float* ws;   // [n_wg][taps][cout][cin]
   float* wsb;  // [n_wg][cout]
+  RowTab rt;   // ragged kernels only; M is then the capacity
 };
 
-template <bool VEC>
+template <bool VEC, bool RAG>
 __global__ __launch_bounds__(256) void k_tconv_wgrad(WgradArgs a) {
   __shared__ __attribute__((aligned(16))) float dyl[WG_SUB][WG_PITCH];
   __shared__ __attribute__((aligned(16))) float xl[WG_SUB + 2 * HALO][WG_PITCH];
   __shared__ int tp[WG_SUB];
+  __shared__ int tl[RAG ? WG_SUB : 1];  // ragged: the series length of the row
   __shared__ float bred[4][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int q = lane >> 4, i = lane & 15;
   const int co_base = blockIdx.y * 64, ci_base = blockIdx.z * 64;
   const int half = a.taps >> 1;
   const int64_t r_lo = (int64_t)blockIdx.x * a.rows_per_wg;
-  const int64_t r_hi = min(a.M, r_lo + a.rows_per_wg);
+  int64_t Mv = a.M;
+  if constexpr (RAG) Mv = live_rows(a.M, a.rt.n_rows);
+  // a chunk past the live rows runs no step and writes a slot of zeros
+  const int64_t r_hi = min(Mv, r_lo + a.rows_per_wg);
 
   floatx4 acc[MAXTAPS][4];
 #pragma unroll
@@ -277,7 +338,7 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad(WgradArgs a) {
         const int64_t g = g0 - HALO + r;
         const int ci = ci_base + c4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g >= 0 && g < a.M && ci < a.cin)
+        if (g >= 0 && g < Mv && ci < a.cin)
           v = *reinterpret_cast<const float4*>(a.x + g * a.cin + ci);
         *reinterpret_cast<float4*>(&xl[r][c4]) = v;
       }
@@ -290,12 +351,18 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad(WgradArgs a) {
       for (int r = sr; r < WG_SUB + 2 * HALO; r += 4) {
         const int64_t g = g0 - HALO + r;
         const int ci = ci_base + sc;
-        xl[r][sc] = (g >= 0 && g < a.M && ci < a.cin) ? a.x[g * a.cin + ci] : 0.f;
+        xl[r][sc] = (g >= 0 && g < Mv && ci < a.cin) ? a.x[g * a.cin + ci] : 0.f;
       }
     }
     if (threadIdx.x < WG_SUB) {
       const int64_t g = g0 + threadIdx.x;
-      tp[threadIdx.x] = g < r_hi ? (int)(g % a.T) : -(1 << 20);
+      if constexpr (RAG) {
+        const int2 e = g < r_hi ? a.rt.tab[g] : make_int2(0, 0);
+        tp[threadIdx.x] = e.x;
+        tl[threadIdx.x] = e.y;
+      } else {
+        tp[threadIdx.x] = g < r_hi ? (int)(g % a.T) : -(1 << 20);
+      }
     }
     __syncthreads();
     if (blockIdx.z == 0) {
@@ -306,10 +373,11 @@ __global__ __launch_bounds__(256) void k_tconv_wgrad(WgradArgs a) {
       const int gl = 4 * s + q;
       const float av = dyl[gl][wave * 16 + i];
       const int t = tp[gl];
+      const int tT = RAG ? tl[gl] : a.T;
 #pragma unroll
       for (int k = 0; k < MAXTAPS; ++k) {
         if (k < a.taps) {
-          const bool ok = (unsigned)(t + k - half) < (unsigned)a.T;
+          const bool ok = (unsigned)(t + k - half) < (unsigned)tT;
 #pragma unroll
           for (int cj = 0; cj < 4; ++cj) {
             if (ci_base + cj * 16 < a.cin) {
@@ -403,22 +471,49 @@ __global__ void k_tconv_wreduce(WreduceArgs a) {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// Ragged pool / readout: where a row's series lives in the stage before (in)
+// and after (out) the pool (hlhgat_tseries_map)
+struct SeriesTab {
+  const int32_t* soff_in;   // [S + 1] series offsets of the kernel's input rows
+  const int32_t* soff_out;  // [S + 1] of its output rows
+  const int2* tab;          // (step, length) of the rows the kernel's threads own
+  const int32_t* sid;       // series of those rows
+  const int32_t* n_rows;    // their valid prefix
+};
+
+template <bool RAG>
 __global__ void k_leaky_maxpool_fwd(const float* __restrict__ x, int64_t N, int T, int C, int m,
                                     int To, float slope, float* __restrict__ y,
-                                    int32_t* __restrict__ idx) {
+                                    int32_t* __restrict__ idx, SeriesTab st) {
   const int s = m - 1, p = (m - 1) / 2;
   const int64_t total = N * To * C;
+  int64_t Mv = N * To;
+  if constexpr (RAG) Mv = live_rows(Mv, st.n_rows);
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
        j += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(j % C);
     const int64_t no = j / C;
-    const int o = (int)(no % To);
-    const int64_t n = no / To;
+    int o;
+    int64_t base;  // the first input row of the series
+    if constexpr (RAG) {
+      if (no >= Mv) {
+        y[j] = 0.f;
+        idx[j] = 0;
+        continue;
+      }
+      const int n = st.sid[no];
+      o = st.tab[no].x;
+      base = st.soff_in[n];
+      T = st.soff_in[n + 1] - (int)base;
+    } else {
+      o = (int)(no % To);
+      base = (no / To) * T;
+    }
     const int t0 = max(o * s - p, 0), t1 = min(o * s - p + m, T);
     float best = -INFINITY;
     int bi = t0;
     for (int t = t0; t < t1; ++t) {
-      const float v = leaky(x[(n * T + t) * C + c], slope);
+      const float v = leaky(x[(base + t) * C + c], slope);
       if (v > best || v != v) {
         best = v;
         bi = t;
@@ -429,24 +524,41 @@ __global__ void k_leaky_maxpool_fwd(const float* __restrict__ x, int64_t N, int 
   }
 }
 
+template <bool RAG>
 __global__ void k_leaky_maxpool_bwd(const float* __restrict__ x, const float* __restrict__ dy,
                                     const int32_t* __restrict__ idx, int64_t N, int T, int C,
-                                    int m, int To, float slope, float* __restrict__ dx) {
+                                    int m, int To, float slope, float* __restrict__ dx,
+                                    SeriesTab st) {
   const int s = m - 1, p = (m - 1) / 2;
   const int64_t total = N * T * C;
+  int64_t Mv = N * T;
+  if constexpr (RAG) Mv = live_rows(Mv, st.n_rows);
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
        j += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(j % C);
     const int64_t nt = j / C;
-    const int t = (int)(nt % T);
-    const int64_t n = nt / T;
+    int t;
+    int64_t base;  // the first pooled row of the series
+    if constexpr (RAG) {
+      if (nt >= Mv) {
+        dx[j] = 0.f;
+        continue;
+      }
+      const int n = st.sid[nt];
+      t = st.tab[nt].x;
+      base = st.soff_out[n];
+      To = st.soff_out[n + 1] - (int)base;
+    } else {
+      t = (int)(nt % T);
+      base = (nt / T) * To;
+    }
     // windows o with o*s - p <= t <= o*s - p + m - 1
     const int num = t + p - m + 1;
     int o_lo = num <= 0 ? 0 : (num + s - 1) / s;
     int o_hi = min((t + p) / s, To - 1);
     float gsum = 0.f;
     for (int o = o_lo; o <= o_hi; ++o) {
-      const int64_t jo = (n * To + o) * C + c;
+      const int64_t jo = (base + o) * C + c;
       if (idx[jo] == t) gsum += dy[jo];
     }
     dx[j] = x[j] > 0.f ? gsum : gsum * slope;
@@ -456,18 +568,24 @@ __global__ void k_leaky_maxpool_bwd(const float* __restrict__ x, const float* __
 // ---------------------------------------------------------------------------
 // LeakyReLU + [max_t | mean_t] readout (:509-513): y [N, 2C]
 // ---------------------------------------------------------------------------
+template <bool RAG>
 __global__ void k_time_readout_fwd(const float* __restrict__ x, int64_t N, int T, int C,
                                    float slope, float* __restrict__ y,
-                                   int32_t* __restrict__ idx) {
+                                   int32_t* __restrict__ idx, SeriesTab st) {
   const int64_t total = N * C;
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
        j += (int64_t)gridDim.x * blockDim.x) {
     const int64_t n = j / C;
     const int c = (int)(j - n * C);
+    int64_t base = n * T;
+    if constexpr (RAG) {
+      base = st.soff_in[n];
+      T = st.soff_in[n + 1] - (int)base;
+    }
     float best = -INFINITY, sum = 0.f;
     int bi = 0;
     for (int t = 0; t < T; ++t) {
-      const float v = leaky(x[(n * T + t) * C + c], slope);
+      const float v = leaky(x[(base + t) * C + c], slope);
       if (v > best || v != v) {
         best = v;
         bi = t;
@@ -480,16 +598,32 @@ __global__ void k_time_readout_fwd(const float* __restrict__ x, int64_t N, int T
   }
 }
 
+template <bool RAG>
 __global__ void k_time_readout_bwd(const float* __restrict__ x, const float* __restrict__ dy,
                                    const int32_t* __restrict__ idx, int64_t N, int T, int C,
-                                   float slope, float* __restrict__ dx) {
+                                   float slope, float* __restrict__ dx, SeriesTab st) {
   const int64_t total = N * T * C;
+  int64_t Mv = N * T;
+  if constexpr (RAG) Mv = live_rows(Mv, st.n_rows);
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
        j += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(j % C);
     const int64_t nt = j / C;
-    const int t = (int)(nt % T);
-    const int64_t n = nt / T;
+    int t;
+    int64_t n;
+    if constexpr (RAG) {
+      if (nt >= Mv) {
+        dx[j] = 0.f;
+        continue;
+      }
+      n = st.sid[nt];
+      const int2 e = st.tab[nt];
+      t = e.x;
+      T = e.y;
+    } else {
+      t = (int)(nt % T);
+      n = nt / T;
+    }
     float g = dy[n * 2 * C + C + c] / (float)T;
     if (idx[n * C + c] == t) g += dy[n * 2 * C + c];
     dx[j] = x[j] > 0.f ? g : g * slope;
@@ -519,6 +653,157 @@ inline const char* shape_err(int64_t n, int64_t t, int64_t c) {
   if (c < 1 || c > (1 << 20)) return "C must be in [1, 2^20]";
   if (n * t > ((int64_t)1 << 31) - 1024) return "N*T too large";
   return nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// hlhgat_tseries_map: the tables of the ragged layout, from tlen alone
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int pool_len(int t, int m) {  // hlhgat_maxpool_time_len
+  const int s = m - 1, p = (m - 1) / 2;
+  const int v = t + 2 * p - m;
+  return v < 0 ? 0 : v / s + 1;
+}
+
+constexpr int SCAN_T = 1024;
+
+// One workgroup: the exclusive prefix sums of the (clamped) lengths of both
+// stages.  Thread i owns a contiguous run of series; the runs' totals are
+// scanned in LDS.  Integer sums: any order gives the same result.
+__global__ __launch_bounds__(SCAN_T) void k_tseries_scan(const int32_t* __restrict__ tlen, int S,
+                                                         int t_max, int m,
+                                                         int32_t* __restrict__ soff0,
+                                                         int32_t* __restrict__ soff1,
+                                                         int32_t* __restrict__ n_rows,
+                                                         unsigned* err) {
+  __shared__ int p0[SCAN_T], p1[SCAN_T];
+  const int tid = threadIdx.x;
+  const int per = (S + SCAN_T - 1) / SCAN_T;
+  const int lo = min(S, tid * per), hi = min(S, lo + per);
+  int a0 = 0, a1 = 0;
+  bool bad = false;
+  for (int s = lo; s < hi; ++s) {
+    int l = tlen[s];
+    if (l < 1 || l > t_max) {
+      bad = true;
+      l = l < 1 ? 1 : t_max;
+    }
+    a0 += l;
+    a1 += pool_len(l, m);
+  }
+  p0[tid] = a0;
+  p1[tid] = a1;
+  __syncthreads();
+  for (int d = 1; d < SCAN_T; d <<= 1) {  // inclusive scan of the runs' totals
+    const int v0 = tid >= d ? p0[tid - d] : 0, v1 = tid >= d ? p1[tid - d] : 0;
+    __syncthreads();
+    p0[tid] += v0;
+    p1[tid] += v1;
+    __syncthreads();
+  }
+  int b0 = p0[tid] - a0, b1 = p1[tid] - a1;
+  for (int s = lo; s < hi; ++s) {
+    int l = tlen[s];
+    l = l < 1 ? 1 : (l > t_max ? t_max : l);
+    soff0[s] = b0;
+    soff1[s] = b1;
+    b0 += l;
+    b1 += pool_len(l, m);
+  }
+  if (tid == SCAN_T - 1) {
+    soff0[S] = p0[tid];
+    soff1[S] = p1[tid];
+    n_rows[0] = p0[tid];
+    n_rows[1] = p1[tid];
+  }
+  if (bad && err) {
+    // host memory without PCIe atomics: load + store keeps the other bits
+    const unsigned old = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(err, old | (unsigned)HLHGAT_DEVERR_TSERIES_LEN, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// Thread j = s * t_max + t writes the table entry of step t of series s (both
+// stages) and, as row j, the dead entry of a row past the valid prefix: every
+// row of both tables is written exactly once.
+__global__ void k_tseries_rows(int S, int t_max, int t_max1, const int32_t* __restrict__ soff0,
+                               const int32_t* __restrict__ soff1, int2* __restrict__ tab0,
+                               int32_t* __restrict__ sid0, int2* __restrict__ tab1,
+                               int32_t* __restrict__ sid1) {
+  const int64_t cap0 = (int64_t)S * t_max, cap1 = (int64_t)S * t_max1;
+  const int64_t n0 = soff0[S], n1 = soff1[S];
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < cap0;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    const int s = (int)(j / t_max), t = (int)(j - (int64_t)s * t_max);
+    const int o0 = soff0[s], l0 = soff0[s + 1] - o0;
+    if (t < l0) {
+      tab0[o0 + t] = make_int2(t, l0);
+      sid0[o0 + t] = s;
+    }
+    const int o1 = soff1[s], l1 = soff1[s + 1] - o1;
+    if (t < l1) {
+      tab1[o1 + t] = make_int2(t, l1);
+      sid1[o1 + t] = s;
+    }
+    if (j >= n0) {
+      tab0[j] = make_int2(0, 0);
+      sid0[j] = 0;
+    }
+    if (j >= n1 && j < cap1) {
+      tab1[j] = make_int2(0, 0);
+      sid1[j] = 0;
+    }
+  }
+}
+
+// padded [S, ldx] -> compact [cap] (dead rows 0), or (inverse) compact ->
+// padded with zeros past each series' length: the gradient of the former
+__global__ void k_tseries_pack(const float* __restrict__ src, int64_t ldx, int S, int t_max,
+                               SeriesTab st, int inverse, float* __restrict__ dst) {
+  if (inverse) {
+    const int64_t total = (int64_t)S * ldx;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
+         j += (int64_t)gridDim.x * blockDim.x) {
+      const int s = (int)(j / ldx), t = (int)(j - (int64_t)s * ldx);
+      const int o = st.soff_in[s], l = st.soff_in[s + 1] - o;
+      dst[j] = t < l ? src[o + t] : 0.f;
+    }
+  } else {
+    const int64_t cap = (int64_t)S * t_max;
+    const int64_t Mv = live_rows(cap, st.n_rows);
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < cap;
+         j += (int64_t)gridDim.x * blockDim.x)
+      dst[j] = j < Mv ? src[(int64_t)st.sid[j] * ldx + st.tab[j].x] : 0.f;
+  }
+}
+
+// what every ragged entry asks of its map; stage 0: before the pool, 1: after
+inline const char* map_err(const hlhgat_tseries_t* mp, int stage) {
+  if (!mp) return "NULL map";
+  if (stage < 0 || stage > 1) return "stage must be 0 or 1";
+  if (mp->n_series < 0) return "S < 0";
+  if (mp->t_max[0] < 1 || mp->t_max[0] > (1 << 20)) return "t_max must be in [1, 2^20]";
+  if (mp->pool < 2 || mp->pool > 64) return "pool window must be in [2, 64]";
+  if (mp->t_max[1] != hlhgat_maxpool_time_len(mp->t_max[0], mp->pool) || mp->t_max[1] < 1 ||
+      hlhgat_maxpool_time_len(1, mp->pool) < 1)
+    return "t_max[1] is not the pooled length of t_max[0] (or a series of one step pools to "
+           "nothing)";
+  if (mp->n_series * mp->t_max[0] > ((int64_t)1 << 31) - 1024) return "S * t_max too large";
+  for (int i = 0; i < 2; ++i)
+    if (!mp->soff[i] || !mp->tab[i] || !mp->sid[i]) return "NULL table";
+  if (!mp->n_rows) return "NULL table";
+  return nullptr;
+}
+
+inline RowTab row_tab(const hlhgat_tseries_t* mp, int stage) {
+  return RowTab{reinterpret_cast<const int2*>(mp->tab[stage]), mp->n_rows + stage};
+}
+
+// the tables of a kernel whose threads own rows of `own` and whose series
+// offsets before / after are those of stages `in` / `out`
+inline SeriesTab series_tab(const hlhgat_tseries_t* mp, int in, int out, int own) {
+  return SeriesTab{mp->soff[in], mp->soff[out], reinterpret_cast<const int2*>(mp->tab[own]),
+                   mp->sid[own], mp->n_rows + own};
 }
 
 }  // namespace
@@ -556,9 +841,12 @@ extern "C" int hlhgat_tconv_pack(int nb, const float* const* w, const int64_t* c
   return HLHGAT_OK;
 }
 
-extern "C" int hlhgat_tconv_fwd(const float* x, int64_t n, int64_t t, int64_t cin,
-                                const float* wp, const float* bias, int64_t cout, int taps,
-                                int64_t n1, int64_t n3, float* y, void* stream) {
+// The entries below come in pairs: the dense one, and the ragged one that
+// passes its map's row table (rt); n and t are then the map's series count
+// and capacity per series.
+static int tconv_fwd_impl(const float* x, int64_t n, int64_t t, int64_t cin, const float* wp,
+                          const float* bias, int64_t cout, int taps, int64_t n1, int64_t n3,
+                          float* y, const RowTab* rt, void* stream) {
   HLH_CHECK_ARG(taps_ok(taps), "tconv_fwd: taps=%d must be odd and <= %d", taps, MAXTAPS);
   const char* e = shape_err(n, t, cin);
   HLH_CHECK_ARG(!e, "tconv_fwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n, (long long)t,
@@ -568,21 +856,43 @@ extern "C" int hlhgat_tconv_fwd(const float* x, int64_t n, int64_t t, int64_t ci
   HLH_CHECK_ARG(n1 >= 0 && n3 >= 0 && n1 + n3 <= cout, "tconv_fwd: bad n1/n3");
   HLH_CHECK_ARG(x && wp && y, "tconv_fwd: NULL pointer");
   if (n == 0) return HLHGAT_OK;
-  ConvArgs a{x, n * t, (int)t, (int)cin, (int)cout, taps, wp, bias, y, (int)n1, (int)n3, 0, 0};
+  ConvArgs a{x, n * t, (int)t, (int)cin, (int)cout, taps, wp, bias, y, (int)n1, (int)n3, 0, 0,
+             rt ? *rt : RowTab{}};
   a.vec_in = (cin % 4) == 0 && aligned16(x) && aligned16(wp);
   a.vec_out = (cout % 4) == 0 && aligned16(y);
   const dim3 grid((unsigned)ceil_div(a.M, TM), (unsigned)ceil_div(cout, 64));
-  if (a.vec_in)
-    hipLaunchKernelGGL(k_tconv_fwd<true>, grid, dim3(256), 0, as_stream(stream), a);
+  if (rt && a.vec_in)
+    hipLaunchKernelGGL((k_tconv_fwd<true, true>), grid, dim3(256), 0, as_stream(stream), a);
+  else if (rt)
+    hipLaunchKernelGGL((k_tconv_fwd<false, true>), grid, dim3(256), 0, as_stream(stream), a);
+  else if (a.vec_in)
+    hipLaunchKernelGGL((k_tconv_fwd<true, false>), grid, dim3(256), 0, as_stream(stream), a);
   else
-    hipLaunchKernelGGL(k_tconv_fwd<false>, grid, dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL((k_tconv_fwd<false, false>), grid, dim3(256), 0, as_stream(stream), a);
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }
 
-extern "C" int hlhgat_tconv_embed_fwd(const float* x, int64_t n, int64_t t, const float* w,
-                                      const float* bias, int64_t c, int taps, float* y,
-                                      void* stream) {
+extern "C" int hlhgat_tconv_fwd(const float* x, int64_t n, int64_t t, int64_t cin,
+                                const float* wp, const float* bias, int64_t cout, int taps,
+                                int64_t n1, int64_t n3, float* y, void* stream) {
+  return tconv_fwd_impl(x, n, t, cin, wp, bias, cout, taps, n1, n3, y, nullptr, stream);
+}
+
+extern "C" int hlhgat_tconv_fwd_ragged(const float* x, const hlhgat_tseries_t* map, int stage,
+                                       int64_t cin, const float* wp, const float* bias,
+                                       int64_t cout, int taps, int64_t n1, int64_t n3, float* y,
+                                       void* stream) {
+  const char* e = map_err(map, stage);
+  HLH_CHECK_ARG(!e, "tconv_fwd_ragged: %s", e);
+  const RowTab rt = row_tab(map, stage);
+  return tconv_fwd_impl(x, map->n_series, map->t_max[stage], cin, wp, bias, cout, taps, n1, n3, y,
+                        &rt, stream);
+}
+
+static int tconv_embed_impl(const float* x, int64_t n, int64_t t, const float* w,
+                            const float* bias, int64_t c, int taps, float* y, const RowTab* rt,
+                            void* stream) {
   HLH_CHECK_ARG(taps_ok(taps), "tconv_embed_fwd: taps=%d must be odd and <= %d", taps, MAXTAPS);
   const char* e = shape_err(n, t, c);
   HLH_CHECK_ARG(!e, "tconv_embed_fwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
@@ -594,9 +904,15 @@ extern "C" int hlhgat_tconv_embed_fwd(const float* x, int64_t n, int64_t t, cons
   const int64_t total = ceil_div(M, EMB_R) * (v4 ? c / 4 : c);
   const dim3 grid(flat_grid(total));
   const bool small = total < ((int64_t)1 << 31) - ((int64_t)1 << 28);  // 32-bit index math
-#define HLH_EMBED(V, I)                                                                 \
-  hipLaunchKernelGGL((k_tconv_embed_fwd<V, I>), grid, dim3(256), 0, as_stream(stream), x, M, \
-                     (int)t, w, bias, (int)c, taps, y)
+#define HLH_EMBED(V, I)                                                                     \
+  do {                                                                                      \
+    if (rt)                                                                                 \
+      hipLaunchKernelGGL((k_tconv_embed_fwd<V, I, true>), grid, dim3(256), 0,               \
+                         as_stream(stream), x, M, (int)t, w, bias, (int)c, taps, y, *rt);   \
+    else                                                                                    \
+      hipLaunchKernelGGL((k_tconv_embed_fwd<V, I, false>), grid, dim3(256), 0,              \
+                         as_stream(stream), x, M, (int)t, w, bias, (int)c, taps, y, RowTab{}); \
+  } while (0)
   if (v4 && small)
     HLH_EMBED(4, uint32_t);
   else if (v4)
@@ -610,6 +926,21 @@ extern "C" int hlhgat_tconv_embed_fwd(const float* x, int64_t n, int64_t t, cons
   return HLHGAT_OK;
 }
 
+extern "C" int hlhgat_tconv_embed_fwd(const float* x, int64_t n, int64_t t, const float* w,
+                                      const float* bias, int64_t c, int taps, float* y,
+                                      void* stream) {
+  return tconv_embed_impl(x, n, t, w, bias, c, taps, y, nullptr, stream);
+}
+
+extern "C" int hlhgat_tconv_embed_fwd_ragged(const float* x, const hlhgat_tseries_t* map,
+                                             const float* w, const float* bias, int64_t c,
+                                             int taps, float* y, void* stream) {
+  const char* e = map_err(map, 0);
+  HLH_CHECK_ARG(!e, "tconv_embed_fwd_ragged: %s", e);
+  const RowTab rt = row_tab(map, 0);
+  return tconv_embed_impl(x, map->n_series, map->t_max[0], w, bias, c, taps, y, &rt, stream);
+}
+
 extern "C" int64_t hlhgat_tconv_bwd_weight_workspace_floats(int64_t n, int64_t t, int64_t cin,
                                                             int64_t cout, int taps) {
   if (!taps_ok(taps) || shape_err(n, t, cin) || cout < 1) return 0;
@@ -617,11 +948,11 @@ extern "C" int64_t hlhgat_tconv_bwd_weight_workspace_floats(int64_t n, int64_t t
   return (int64_t)p.n_wg * (taps * cout * cin + cout);
 }
 
-extern "C" int hlhgat_tconv_bwd_weight(const float* x, const float* dy, int64_t n, int64_t t,
-                                       int64_t cin, int64_t cout, int taps, int nb,
-                                       float* const* dw, const int64_t* cout_b,
-                                       const int32_t* taps_b, float* dbias, float* workspace,
-                                       int64_t workspace_floats, void* stream) {
+static int tconv_bwd_weight_impl(const float* x, const float* dy, int64_t n, int64_t t,
+                                 int64_t cin, int64_t cout, int taps, int nb, float* const* dw,
+                                 const int64_t* cout_b, const int32_t* taps_b, float* dbias,
+                                 float* workspace, int64_t workspace_floats, const RowTab* rt,
+                                 void* stream) {
   HLH_CHECK_ARG(taps_ok(taps), "tconv_bwd_weight: taps=%d must be odd and <= %d", taps,
                 MAXTAPS);
   const char* e = shape_err(n, t, cin);
@@ -652,16 +983,19 @@ extern "C" int hlhgat_tconv_bwd_weight(const float* x, const float* dy, int64_t 
   const WgPlan p = wg_plan(M);
   const int64_t nw = taps * cout * cin;
   WgradArgs a{x, dy, M, p.rows_per_wg, (int)t, (int)cin, (int)cout, taps, workspace,
-              workspace + (int64_t)p.n_wg * nw};
+              workspace + (int64_t)p.n_wg * nw, rt ? *rt : RowTab{}};
   const unsigned gy = (unsigned)ceil_div(cout, 64), gz = (unsigned)ceil_div(cin, 64);
   HLH_CHECK_ARG(gy <= 65535 && gz <= 65535, "tconv_bwd_weight: too many channel tiles");
   const bool vec = (cin % 4) == 0 && (cout % 4) == 0 && aligned16(x) && aligned16(dy);
-  if (vec)
-    hipLaunchKernelGGL(k_tconv_wgrad<true>, dim3((unsigned)p.n_wg, gy, gz), dim3(256), 0,
-                       as_stream(stream), a);
+  const dim3 wgrid((unsigned)p.n_wg, gy, gz);
+  if (rt && vec)
+    hipLaunchKernelGGL((k_tconv_wgrad<true, true>), wgrid, dim3(256), 0, as_stream(stream), a);
+  else if (rt)
+    hipLaunchKernelGGL((k_tconv_wgrad<false, true>), wgrid, dim3(256), 0, as_stream(stream), a);
+  else if (vec)
+    hipLaunchKernelGGL((k_tconv_wgrad<true, false>), wgrid, dim3(256), 0, as_stream(stream), a);
   else
-    hipLaunchKernelGGL(k_tconv_wgrad<false>, dim3((unsigned)p.n_wg, gy, gz), dim3(256), 0,
-                       as_stream(stream), a);
+    hipLaunchKernelGGL((k_tconv_wgrad<false, false>), wgrid, dim3(256), 0, as_stream(stream), a);
   HLH_CHECK_LAUNCH();
   r.ws = a.ws;
   r.wsb = a.wsb;
@@ -677,6 +1011,29 @@ extern "C" int hlhgat_tconv_bwd_weight(const float* x, const float* dy, int64_t 
   return HLHGAT_OK;
 }
 
+extern "C" int hlhgat_tconv_bwd_weight(const float* x, const float* dy, int64_t n, int64_t t,
+                                       int64_t cin, int64_t cout, int taps, int nb,
+                                       float* const* dw, const int64_t* cout_b,
+                                       const int32_t* taps_b, float* dbias, float* workspace,
+                                       int64_t workspace_floats, void* stream) {
+  return tconv_bwd_weight_impl(x, dy, n, t, cin, cout, taps, nb, dw, cout_b, taps_b, dbias,
+                               workspace, workspace_floats, nullptr, stream);
+}
+
+extern "C" int hlhgat_tconv_bwd_weight_ragged(const float* x, const float* dy,
+                                              const hlhgat_tseries_t* map, int stage,
+                                              int64_t cin, int64_t cout, int taps, int nb,
+                                              float* const* dw, const int64_t* cout_b,
+                                              const int32_t* taps_b, float* dbias,
+                                              float* workspace, int64_t workspace_floats,
+                                              void* stream) {
+  const char* e = map_err(map, stage);
+  HLH_CHECK_ARG(!e, "tconv_bwd_weight_ragged: %s", e);
+  const RowTab rt = row_tab(map, stage);
+  return tconv_bwd_weight_impl(x, dy, map->n_series, map->t_max[stage], cin, cout, taps, nb, dw,
+                               cout_b, taps_b, dbias, workspace, workspace_floats, &rt, stream);
+}
+
 extern "C" int64_t hlhgat_maxpool_time_len(int64_t t, int m) {
   if (t < 1 || m < 2) return 0;
   const int64_t s = m - 1, p = (m - 1) / 2;
@@ -684,9 +1041,8 @@ extern "C" int64_t hlhgat_maxpool_time_len(int64_t t, int m) {
   return v < 0 ? 0 : v / s + 1;
 }
 
-extern "C" int hlhgat_leaky_maxpool_time_fwd(const float* x, int64_t n, int64_t t, int64_t c,
-                                             int m, float slope, float* y, int32_t* idx,
-                                             void* stream) {
+static int maxpool_fwd_impl(const float* x, int64_t n, int64_t t, int64_t c, int m, float slope,
+                            float* y, int32_t* idx, const SeriesTab* st, void* stream) {
   const char* e = shape_err(n, t, c);
   HLH_CHECK_ARG(!e, "leaky_maxpool_time_fwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
                 (long long)t, (long long)c);
@@ -695,16 +1051,36 @@ extern "C" int hlhgat_leaky_maxpool_time_fwd(const float* x, int64_t n, int64_t 
   HLH_CHECK_ARG(to >= 1, "leaky_maxpool_time_fwd: T=%lld shorter than the window", (long long)t);
   HLH_CHECK_ARG(x && y && idx, "leaky_maxpool_time_fwd: NULL pointer");
   if (n == 0) return HLHGAT_OK;
-  hipLaunchKernelGGL(k_leaky_maxpool_fwd, dim3(flat_grid(n * to * c)), dim3(256), 0,
-                     as_stream(stream), x, n, (int)t, (int)c, m, (int)to, slope, y, idx);
+  if (st)
+    hipLaunchKernelGGL(k_leaky_maxpool_fwd<true>, dim3(flat_grid(n * to * c)), dim3(256), 0,
+                       as_stream(stream), x, n, (int)t, (int)c, m, (int)to, slope, y, idx, *st);
+  else
+    hipLaunchKernelGGL(k_leaky_maxpool_fwd<false>, dim3(flat_grid(n * to * c)), dim3(256), 0,
+                       as_stream(stream), x, n, (int)t, (int)c, m, (int)to, slope, y, idx,
+                       SeriesTab{});
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }
 
-extern "C" int hlhgat_leaky_maxpool_time_bwd(const float* x, const float* dy,
-                                             const int32_t* idx, int64_t n, int64_t t,
-                                             int64_t c, int m, float slope, float* dx,
+extern "C" int hlhgat_leaky_maxpool_time_fwd(const float* x, int64_t n, int64_t t, int64_t c,
+                                             int m, float slope, float* y, int32_t* idx,
                                              void* stream) {
+  return maxpool_fwd_impl(x, n, t, c, m, slope, y, idx, nullptr, stream);
+}
+
+extern "C" int hlhgat_leaky_maxpool_time_fwd_ragged(const float* x, const hlhgat_tseries_t* map,
+                                                    int64_t c, float slope, float* y,
+                                                    int32_t* idx, void* stream) {
+  const char* e = map_err(map, 0);
+  HLH_CHECK_ARG(!e, "leaky_maxpool_time_fwd_ragged: %s", e);
+  const SeriesTab st = series_tab(map, 0, 1, 1);
+  return maxpool_fwd_impl(x, map->n_series, map->t_max[0], c, map->pool, slope, y, idx, &st,
+                          stream);
+}
+
+static int maxpool_bwd_impl(const float* x, const float* dy, const int32_t* idx, int64_t n,
+                            int64_t t, int64_t c, int m, float slope, float* dx,
+                            const SeriesTab* st, void* stream) {
   const char* e = shape_err(n, t, c);
   HLH_CHECK_ARG(!e, "leaky_maxpool_time_bwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
                 (long long)t, (long long)c);
@@ -713,21 +1089,81 @@ extern "C" int hlhgat_leaky_maxpool_time_bwd(const float* x, const float* dy,
   HLH_CHECK_ARG(to >= 1, "leaky_maxpool_time_bwd: T=%lld shorter than the window", (long long)t);
   HLH_CHECK_ARG(x && dy && idx && dx, "leaky_maxpool_time_bwd: NULL pointer");
   if (n == 0) return HLHGAT_OK;
-  hipLaunchKernelGGL(k_leaky_maxpool_bwd, dim3(flat_grid(n * t * c)), dim3(256), 0,
-                     as_stream(stream), x, dy, idx, n, (int)t, (int)c, m, (int)to, slope, dx);
+  if (st)
+    hipLaunchKernelGGL(k_leaky_maxpool_bwd<true>, dim3(flat_grid(n * t * c)), dim3(256), 0,
+                       as_stream(stream), x, dy, idx, n, (int)t, (int)c, m, (int)to, slope, dx,
+                       *st);
+  else
+    hipLaunchKernelGGL(k_leaky_maxpool_bwd<false>, dim3(flat_grid(n * t * c)), dim3(256), 0,
+                       as_stream(stream), x, dy, idx, n, (int)t, (int)c, m, (int)to, slope, dx,
+                       SeriesTab{});
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_leaky_maxpool_time_bwd(const float* x, const float* dy,
+                                             const int32_t* idx, int64_t n, int64_t t,
+                                             int64_t c, int m, float slope, float* dx,
+                                             void* stream) {
+  return maxpool_bwd_impl(x, dy, idx, n, t, c, m, slope, dx, nullptr, stream);
+}
+
+extern "C" int hlhgat_leaky_maxpool_time_bwd_ragged(const float* x, const float* dy,
+                                                    const int32_t* idx,
+                                                    const hlhgat_tseries_t* map, int64_t c,
+                                                    float slope, float* dx, void* stream) {
+  const char* e = map_err(map, 0);
+  HLH_CHECK_ARG(!e, "leaky_maxpool_time_bwd_ragged: %s", e);
+  const SeriesTab st = series_tab(map, 0, 1, 0);
+  return maxpool_bwd_impl(x, dy, idx, map->n_series, map->t_max[0], c, map->pool, slope, dx, &st,
+                          stream);
+}
+
+static int readout_fwd_impl(const float* x, int64_t n, int64_t t, int64_t c, float slope,
+                            float* y, int32_t* idx, const SeriesTab* st, void* stream) {
+  const char* e = shape_err(n, t, c);
+  HLH_CHECK_ARG(!e, "time_readout_fwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
+                (long long)t, (long long)c);
+  HLH_CHECK_ARG(x && y && idx, "time_readout_fwd: NULL pointer");
+  if (n == 0) return HLHGAT_OK;
+  if (st)
+    hipLaunchKernelGGL(k_time_readout_fwd<true>, dim3(flat_grid(n * c)), dim3(256), 0,
+                       as_stream(stream), x, n, (int)t, (int)c, slope, y, idx, *st);
+  else
+    hipLaunchKernelGGL(k_time_readout_fwd<false>, dim3(flat_grid(n * c)), dim3(256), 0,
+                       as_stream(stream), x, n, (int)t, (int)c, slope, y, idx, SeriesTab{});
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }
 
 extern "C" int hlhgat_time_readout_fwd(const float* x, int64_t n, int64_t t, int64_t c,
                                        float slope, float* y, int32_t* idx, void* stream) {
+  return readout_fwd_impl(x, n, t, c, slope, y, idx, nullptr, stream);
+}
+
+extern "C" int hlhgat_time_readout_fwd_ragged(const float* x, const hlhgat_tseries_t* map,
+                                              int64_t c, float slope, float* y, int32_t* idx,
+                                              void* stream) {
+  const char* e = map_err(map, 1);
+  HLH_CHECK_ARG(!e, "time_readout_fwd_ragged: %s", e);
+  const SeriesTab st = series_tab(map, 1, 1, 1);
+  return readout_fwd_impl(x, map->n_series, map->t_max[1], c, slope, y, idx, &st, stream);
+}
+
+static int readout_bwd_impl(const float* x, const float* dy, const int32_t* idx, int64_t n,
+                            int64_t t, int64_t c, float slope, float* dx, const SeriesTab* st,
+                            void* stream) {
   const char* e = shape_err(n, t, c);
-  HLH_CHECK_ARG(!e, "time_readout_fwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
+  HLH_CHECK_ARG(!e, "time_readout_bwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
                 (long long)t, (long long)c);
-  HLH_CHECK_ARG(x && y && idx, "time_readout_fwd: NULL pointer");
+  HLH_CHECK_ARG(x && dy && idx && dx, "time_readout_bwd: NULL pointer");
   if (n == 0) return HLHGAT_OK;
-  hipLaunchKernelGGL(k_time_readout_fwd, dim3(flat_grid(n * c)), dim3(256), 0,
-                     as_stream(stream), x, n, (int)t, (int)c, slope, y, idx);
+  if (st)
+    hipLaunchKernelGGL(k_time_readout_bwd<true>, dim3(flat_grid(n * t * c)), dim3(256), 0,
+                       as_stream(stream), x, dy, idx, n, (int)t, (int)c, slope, dx, *st);
+  else
+    hipLaunchKernelGGL(k_time_readout_bwd<false>, dim3(flat_grid(n * t * c)), dim3(256), 0,
+                       as_stream(stream), x, dy, idx, n, (int)t, (int)c, slope, dx, SeriesTab{});
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }
@@ -735,13 +1171,53 @@ extern "C" int hlhgat_time_readout_fwd(const float* x, int64_t n, int64_t t, int
 extern "C" int hlhgat_time_readout_bwd(const float* x, const float* dy, const int32_t* idx,
                                        int64_t n, int64_t t, int64_t c, float slope, float* dx,
                                        void* stream) {
-  const char* e = shape_err(n, t, c);
-  HLH_CHECK_ARG(!e, "time_readout_bwd: %s (n=%lld T=%lld C=%lld)", e, (long long)n,
-                (long long)t, (long long)c);
-  HLH_CHECK_ARG(x && dy && idx && dx, "time_readout_bwd: NULL pointer");
-  if (n == 0) return HLHGAT_OK;
-  hipLaunchKernelGGL(k_time_readout_bwd, dim3(flat_grid(n * t * c)), dim3(256), 0,
-                     as_stream(stream), x, dy, idx, n, (int)t, (int)c, slope, dx);
+  return readout_bwd_impl(x, dy, idx, n, t, c, slope, dx, nullptr, stream);
+}
+
+extern "C" int hlhgat_time_readout_bwd_ragged(const float* x, const float* dy,
+                                              const int32_t* idx, const hlhgat_tseries_t* map,
+                                              int64_t c, float slope, float* dx, void* stream) {
+  const char* e = map_err(map, 1);
+  HLH_CHECK_ARG(!e, "time_readout_bwd_ragged: %s", e);
+  const SeriesTab st = series_tab(map, 1, 1, 1);
+  return readout_bwd_impl(x, dy, idx, map->n_series, map->t_max[1], c, slope, dx, &st, stream);
+}
+
+// ---------------------------------------------------------------------------
+// the ragged layout's tables
+// ---------------------------------------------------------------------------
+extern "C" int hlhgat_tseries_map(const int32_t* tlen, const hlhgat_tseries_t* map,
+                                  void* stream) {
+  const char* e = map_err(map, 0);
+  HLH_CHECK_ARG(!e, "tseries_map: %s", e);
+  HLH_CHECK_ARG(tlen, "tseries_map: NULL tlen");
+  const int S = (int)map->n_series;
+  hipLaunchKernelGGL(k_tseries_scan, dim3(1), dim3(SCAN_T), 0, as_stream(stream), tlen, S,
+                     (int)map->t_max[0], (int)map->pool, map->soff[0], map->soff[1], map->n_rows,
+                     device_error_word());
+  HLH_CHECK_LAUNCH();
+  if (S == 0) return HLHGAT_OK;
+  hipLaunchKernelGGL(k_tseries_rows, dim3(flat_grid(map->n_series * map->t_max[0])), dim3(256), 0,
+                     as_stream(stream), S, (int)map->t_max[0], (int)map->t_max[1], map->soff[0],
+                     map->soff[1], reinterpret_cast<int2*>(map->tab[0]), map->sid[0],
+                     reinterpret_cast<int2*>(map->tab[1]), map->sid[1]);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+extern "C" int hlhgat_tseries_pack(const float* src, int64_t ldx, const hlhgat_tseries_t* map,
+                                   int inverse, float* dst, void* stream) {
+  const char* e = map_err(map, 0);
+  HLH_CHECK_ARG(!e, "tseries_pack: %s", e);
+  HLH_CHECK_ARG(ldx >= map->t_max[0], "tseries_pack: ldx=%lld < t_max=%lld", (long long)ldx,
+                (long long)map->t_max[0]);
+  HLH_CHECK_ARG(map->n_series * ldx <= ((int64_t)1 << 40), "tseries_pack: S * ldx too large");
+  HLH_CHECK_ARG(src && dst, "tseries_pack: NULL pointer");
+  if (map->n_series == 0) return HLHGAT_OK;
+  const SeriesTab st = series_tab(map, 0, 0, 0);
+  const int64_t total = inverse ? map->n_series * ldx : map->n_series * map->t_max[0];
+  hipLaunchKernelGGL(k_tseries_pack, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), src,
+                     ldx, (int)map->n_series, (int)map->t_max[0], st, inverse, dst);
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;
 }

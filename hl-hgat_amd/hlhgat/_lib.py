@@ -226,7 +226,23 @@ SIGNATURES = {
     "hlhgat_time_readout_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp]),
     "hlhgat_time_readout_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_vp,
                                         c_vp]),
+    "hlhgat_tseries_map": (c_i32, [c_vp, c_vp, c_vp]),
+    "hlhgat_tseries_pack": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "hlhgat_tconv_fwd_ragged": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64,
+                                        c_i64, c_vp, c_vp]),
+    "hlhgat_tconv_embed_fwd_ragged": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "hlhgat_tconv_bwd_weight_ragged": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32,
+                                               c_i32, P_vp, P_i64, P_i32, c_vp, c_vp, c_i64,
+                                               c_vp]),
+    "hlhgat_leaky_maxpool_time_fwd_ragged": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "hlhgat_leaky_maxpool_time_bwd_ragged": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp,
+                                                     c_vp]),
+    "hlhgat_time_readout_fwd_ragged": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "hlhgat_time_readout_bwd_ragged": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp,
+                                               c_vp]),
     "hlhgat_fc_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "hlhgat_fc_prepare_windows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64,
+                                          c_vp, c_vp, c_sz, c_vp]),
     "hlhgat_fc_prepare": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                   c_sz, c_vp]),
     "hlhgat_fc_dense": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
@@ -244,6 +260,7 @@ DEVERR_METRIC_LABEL = 8
 DEVERR_METER_FULL = 16
 DEVERR_EIGPE_SIZE = 32
 DEVERR_MLGC_RANGE = 64
+DEVERR_TSERIES_LEN = 128
 MLGC_ONE_WAY, MLGC_PRUNE_SINGLE, MLGC_DROP_ISOLATED = 1, 2, 4
 LOSS_MEAN, LOSS_SUM, LOSS_FOCAL = 0, 1, 2
 CE_MAX_CLASSES = 64  # HLHGAT_CE_MAX_CLASSES
@@ -274,6 +291,12 @@ class HodgeFactorDesc(C.Structure):
     _fields_ = [("node_rowptr", c_vp), ("node_edge", c_vp), ("node_sign", c_vp),
                 ("node_order", c_vp), ("n_nodes", c_i64), ("ends", c_vp), ("alpha", c_vp),
                 ("edge_order", c_vp), ("n_edges", c_i64)]
+
+
+class TSeriesDesc(C.Structure):
+    """hlhgat_tseries_t (include/hlhgat.h)."""
+    _fields_ = [("n_series", c_i64), ("t_max", c_i64 * 2), ("pool", c_i32),
+                ("soff", c_vp * 2), ("tab", c_vp * 2), ("sid", c_vp * 2), ("n_rows", c_vp)]
 
 
 class PeSideDesc(C.Structure):

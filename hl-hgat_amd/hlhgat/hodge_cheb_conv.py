@@ -408,7 +408,18 @@ class Inception1D(nn.Module):
     channels-last in the HIP kernels of ops.temporal_conv (one launch per
     stage for the three branches), ops.leaky_maxpool_time and
     ops.time_readout, the BatchNorms through ops.batch_norm_act on the
-    [N*T, C] view.  CPU tensors take the torch ops."""
+    [N*T, C] view.  CPU tensors take the torch ops.
+
+    forward(x, lengths) runs series of different lengths in one batch, the
+    per-sample windows of HL-HGAT-DEMO/lib/Hodge_Dataset.py:131-133: x is
+    padded to [N, t_max], lengths int32 [N] on x's device, x[s, lengths[s]:]
+    is never read.  Every series is convolved, pooled and read out on its own
+    length, exactly as the reference does on that series alone; BatchNorm, the
+    only batch-coupled step, takes its training statistics over all valid
+    (series, step) positions (the reference's when the lengths are equal).
+    On a ROCm device the activations are the compact rows of an
+    ops.TimeSeriesMap, of fixed capacity, so no shape depends on the lengths
+    and one captured graph serves every draw."""
 
     def __init__(self, in_channels=64, num_channels=8, maxpool=3, if_dim_reduction=False,
                  leaky_slope=0.1, if_readout=False):
@@ -449,9 +460,54 @@ class Inception1D(nn.Module):
             return ops.time_readout(h, slope)
         return torch.nn.functional.leaky_relu(h, slope)
 
-    def forward(self, x: Tensor) -> Tensor:
+    def _forward_hip_ragged(self, x: Tensor, lengths: Tensor) -> Tensor:
+        slope = self.leakyReLU.negative_slope
+        tm = ops.time_series_map(lengths, x.size(1), self.maxpool)
+        h = ops.time_series_pack(x, tm)
+        h = ops.temporal_conv_ragged(h, tm, 0, [self.embedding.weight], [self.embedding.bias])
+        convs = [self.channel1_1, self.channel2_1, self.channel3_1]
+        h = ops.temporal_conv_ragged(h, tm, 0, [c.weight for c in convs], [c.bias for c in convs])
+        h = ops.batch_norm_act(h, self.bn1, relu=False, valid=tm.valid(0))
+        h = ops.leaky_maxpool_time_ragged(h, tm, slope)
+        convs = [self.channel1_2, self.channel2_2, self.channel3_2]
+        h = ops.temporal_conv_ragged(h, tm, 1, [c.weight for c in convs], [c.bias for c in convs])
+        h = ops.batch_norm_act(h, self.bn2, relu=False, valid=tm.valid(1))
+        return ops.time_readout_ragged(h, tm, slope)
+
+    def _forward_cpu_ragged(self, x: Tensor, lengths: Tensor) -> Tensor:
+        """The reference's ops on every series at its own length; the two
+        BatchNorms see all valid positions as one [1, C, sum len] batch."""
+        lens = [int(v) for v in lengths.tolist()]
+
+        def pooled_bn(bn, hs):
+            y = bn(torch.cat(hs, dim=2))
+            return torch.split(y, [h.size(2) for h in hs], dim=2)
+
+        hs = [self.embedding(x[s:s + 1, :n].unsqueeze(1)) for s, n in enumerate(lens)]
+        hs = [torch.cat((self.channel1_1(h), self.channel2_1(h), self.channel3_1(h)), dim=1)
+              for h in hs]
+        hs = [self.pool_1(self.leakyReLU(h)) for h in pooled_bn(self.bn1, hs)]
+        hs = [torch.cat((self.channel1_2(h), self.channel2_2(h), self.channel3_2(h)), dim=1)
+              for h in hs]
+        hs = [self.leakyReLU(h) for h in pooled_bn(self.bn2, hs)]
+        return torch.cat([torch.cat([h.max(dim=-1)[0], h.mean(dim=-1)], dim=-1) for h in hs])
+
+    def _forward_ragged(self, x: Tensor, lengths: Tensor) -> Tensor:
+        if not self.if_readout:
+            raise ValueError("Inception1D: lengths needs if_readout=True (series of different "
+                             "lengths have no common [N, T', C] form)")
+        if lengths.dim() != 1 or lengths.numel() != x.size(0) or lengths.device != x.device:
+            raise ValueError(f"Inception1D: lengths must be [{x.size(0)}] on {x.device}, got "
+                             f"{tuple(lengths.shape)} on {lengths.device}")
+        if x.is_cuda:
+            return self._forward_hip_ragged(x, lengths.to(torch.int32))
+        return self._forward_cpu_ragged(x, lengths)
+
+    def forward(self, x: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
         if x.dim() != 2:
             raise ValueError(f"Inception1D expects [N, T] time courses, got {tuple(x.shape)}")
+        if lengths is not None:
+            return self._forward_ragged(x, lengths)
         if x.is_cuda:
             return self._forward_hip(x)
         x = torch.unsqueeze(x, 1)  # N x C x T

@@ -955,7 +955,13 @@ class HL_HGAT_attpool(nn.Module):
                 dn.num_node1, d.num_node1, dev, d.x_t.size(0)))
             pos_ss.append(d.pos_s.to(dev).view(-1).to(torch.float32) + _level_offsets(
                 dn.num_edge1, d.num_edge1, dev, d.x_s.size(0)))
-        x_t = self.node_embedding(data.x_t.to(dev))
+        # per-sample windows (BrainPipeline.batch(window="per_sample")): x_t is
+        # padded to one width and t_len holds every time course's own length
+        t_len = getattr(data, "t_len", None)
+        if torch.is_tensor(t_len):
+            x_t = self.node_embedding(data.x_t.to(dev), t_len.to(dev))
+        else:
+            x_t = self.node_embedding(data.x_t.to(dev))
         x_s = data.x_s.to(dev)
         adj_t = (data.edge_index_t.to(dev), data.edge_weight_t.to(dev))
         adj_s = (data.edge_index_s.to(dev), data.edge_weight_s.to(dev))

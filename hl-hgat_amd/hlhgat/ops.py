@@ -33,6 +33,8 @@ __all__ = [
     "batch_norm_act", "check_device_errors", "clear_device_errors", "device_errors",
     "node_from_edges", "edge_from_nodes", "incidence_mm", "att_score", "segment_mean",
     "temporal_conv", "leaky_maxpool_time", "time_readout", "dropout",
+    "TimeSeriesMap", "time_series_map", "time_series_pack", "temporal_conv_ragged",
+    "leaky_maxpool_time_ragged", "time_readout_ragged",
     "pe_flip", "pe_signs",
     "bce_logits_loss", "cross_entropy", "mse_loss", "average_precision",
     "collect_rows", "f1_per_graph", "argmax_correct", "regression_summary",
@@ -2147,6 +2149,36 @@ def _tconv_pack(weights, cin: int, taps: int, flip: bool) -> torch.Tensor:
     return wp
 
 
+def _tconv_bias(biases, couts, device) -> torch.Tensor:
+    """The branches' biases as one [sum Cout_b] vector."""
+    nb = len(biases)
+    if nb == 1:
+        return biases[0]
+    bias = torch.empty(sum(couts), device=device, dtype=torch.float32)
+    offs = [sum(couts[:b]) for b in range(nb)]
+    one = [1] * nb
+    check(LIB.hlhgat_copy2d_batched(
+        nb, _arr(_lib.c_vp, [b.data_ptr() for b in biases]), _arr(_lib.c_i64, couts),
+        _arr(_lib.c_vp, [bias.data_ptr() + 4 * o for o in offs]),
+        _arr(_lib.c_i64, couts), _arr(_lib.c_i64, one), _arr(_lib.c_i64, couts),
+        _stream(bias)), "copy2d_batched")
+    return bias
+
+
+def _tconv_skip(couts, tbs, taps: int) -> Tuple[int, int]:
+    """(n1, n3): the output columns of the leading 1-tap / 3-tap branches,
+    whose column tiles skip the outer taps."""
+    n1 = n3 = 0
+    b, nb = 0, len(couts)
+    while b < nb and tbs[b] == 1 and taps > 1:
+        n1 += couts[b]
+        b += 1
+    while b < nb and tbs[b] <= 3 and taps > 3:
+        n3 += couts[b]
+        b += 1
+    return n1, n3
+
+
 class _TemporalConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, nb, *params):
@@ -2162,27 +2194,8 @@ class _TemporalConvFn(torch.autograd.Function):
                                              _stream(x)), "tconv_embed_fwd")
         else:
             wp = _tconv_pack(weights, cin, taps, False)
-            bias = None
-            if has_bias and nb == 1:
-                bias = biases[0]
-            elif has_bias:
-                bias = torch.empty(cout, device=x.device, dtype=torch.float32)
-                offs = [sum(couts[:b]) for b in range(nb)]
-                one = [1] * nb
-                check(LIB.hlhgat_copy2d_batched(
-                    nb, _arr(_lib.c_vp, [b.data_ptr() for b in biases]), _arr(_lib.c_i64, couts),
-                    _arr(_lib.c_vp, [bias.data_ptr() + 4 * o for o in offs]),
-                    _arr(_lib.c_i64, couts), _arr(_lib.c_i64, one), _arr(_lib.c_i64, couts),
-                    _stream(x)), "copy2d_batched")
-            # leading 1-tap / 3-tap branches: their column tiles skip the outer taps
-            n1 = n3 = 0
-            b = 0
-            while b < nb and tbs[b] == 1 and taps > 1:
-                n1 += couts[b]
-                b += 1
-            while b < nb and tbs[b] <= 3 and taps > 3:
-                n3 += couts[b]
-                b += 1
+            bias = _tconv_bias(biases, couts, x.device) if has_bias else None
+            n1, n3 = _tconv_skip(couts, tbs, taps)
             check(LIB.hlhgat_tconv_fwd(x.data_ptr(), N, T, cin, wp.data_ptr(), _ptr(bias), cout,
                                        taps, n1, n3, y.data_ptr(), _stream(x)), "tconv_fwd")
         ctx.nb, ctx.has_bias = nb, has_bias
@@ -2321,6 +2334,251 @@ def time_readout(x: torch.Tensor, slope: float) -> torch.Tensor:
     if x.dim() != 3:
         raise RuntimeError(f"hlhgat: time_readout x must be [N, T, C] (got {tuple(x.shape)})")
     return _TimeReadoutFn.apply(x.contiguous(), float(slope))
+
+
+# ----------------------------------------------------------------------------
+# ragged time layout (include/hlhgat.h: hlhgat_tseries_t): series of their own
+# lengths stacked compactly in buffers of fixed capacity
+# ----------------------------------------------------------------------------
+@dataclass
+class TimeSeriesMap:
+    """The device tables of time_series_map.  Stage 0 is the layout before
+    the max-pool, stage 1 the one after it: series s owns rows
+    [soff[i][s], soff[i][s + 1]) of a buffer of n_series * t_max[i] rows, and
+    n_rows[i:i + 1] is the valid-row prefix (ops.batch_norm_act's valid=)."""
+    n_series: int
+    t_max: Tuple[int, int]
+    pool: int
+    soff: Tuple[torch.Tensor, torch.Tensor]
+    tab: Tuple[torch.Tensor, torch.Tensor]
+    sid: Tuple[torch.Tensor, torch.Tensor]
+    n_rows: torch.Tensor
+    desc: "_lib.TSeriesDesc"
+
+    def capacity(self, stage: int) -> int:
+        return self.n_series * self.t_max[stage]
+
+    def valid(self, stage: int) -> torch.Tensor:
+        return self.n_rows[stage:stage + 1]
+
+
+def time_series_map(lengths: torch.Tensor, t_max: int, pool: int = 3) -> TimeSeriesMap:
+    """The ragged layout of series with ``lengths`` (int32 [S], device,
+    1 <= lengths[s] <= t_max; the per-sample window lengths of
+    HL-HGAT-DEMO/lib/Hodge_Dataset.py:131-133) around a max-pool of window
+    ``pool``: every table is built on the device in two launches, nothing is
+    read back.  A length outside [1, t_max] is clamped and reported through
+    check_device_errors."""
+    _req_dev(lengths, "lengths", torch.int32)
+    if lengths.dim() != 1 or not lengths.is_contiguous():
+        raise RuntimeError(f"hlhgat: time_series_map lengths must be contiguous int32 [S] "
+                           f"(got {tuple(lengths.shape)})")
+    S, t0, m = int(lengths.numel()), int(t_max), int(pool)
+    t1 = maxpool_time_len(t0, m) if t0 >= 1 and m >= 2 else 0
+    dev = lengths.device
+    i32 = dict(device=dev, dtype=torch.int32)
+    soff = (torch.empty(S + 1, **i32), torch.empty(S + 1, **i32))
+    tab = (torch.empty((S * max(t0, 0), 2), **i32), torch.empty((S * t1, 2), **i32))
+    sid = (torch.empty(S * max(t0, 0), **i32), torch.empty(S * t1, **i32))
+    n_rows = torch.empty(2, **i32)
+    d = _lib.TSeriesDesc()
+    d.n_series, d.pool = S, m
+    d.t_max[0], d.t_max[1] = t0, t1
+    for i in range(2):
+        d.soff[i], d.tab[i], d.sid[i] = soff[i].data_ptr(), tab[i].data_ptr(), sid[i].data_ptr()
+    d.n_rows = n_rows.data_ptr()
+    check(LIB.hlhgat_tseries_map(lengths.data_ptr(), C.byref(d), _stream(lengths)), "tseries_map")
+    return TimeSeriesMap(S, (t0, t1), m, soff, tab, sid, n_rows, d)
+
+
+class _SeriesPackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, tm):
+        xc = torch.empty(tm.capacity(0), 1, device=x.device, dtype=torch.float32)
+        check(LIB.hlhgat_tseries_pack(x.data_ptr(), x.size(1), C.byref(tm.desc), 0, xc.data_ptr(),
+                                      _stream(x)), "tseries_pack")
+        ctx.tm, ctx.shape = tm, tuple(x.shape)
+        return xc
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        gx = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
+        check(LIB.hlhgat_tseries_pack(g.data_ptr(), ctx.shape[1], C.byref(ctx.tm.desc), 1,
+                                      gx.data_ptr(), _stream(g)), "tseries_unpack")
+        return gx, None
+
+
+def time_series_pack(x: torch.Tensor, tm: TimeSeriesMap) -> torch.Tensor:
+    """The padded time courses x [S, >= t_max] (x[s, lengths[s]:] is never
+    read) as the compact stage-0 column [S * t_max, 1]; the gradient is zero
+    in the padded columns."""
+    _req_dev(x, "x")
+    if x.dim() != 2 or x.size(0) != tm.n_series or x.size(1) < tm.t_max[0]:
+        raise RuntimeError(f"hlhgat: time_series_pack x must be [{tm.n_series}, >= {tm.t_max[0]}] "
+                           f"(got {tuple(x.shape)})")
+    return _SeriesPackFn.apply(x.contiguous(), tm)
+
+
+def _req_rows(x: torch.Tensor, tm: TimeSeriesMap, stage: int, name: str) -> None:
+    _req_dev(x, "x")
+    if x.dim() != 2 or x.size(0) != tm.capacity(stage):
+        raise RuntimeError(f"hlhgat: {name} x must be [{tm.capacity(stage)}, C] rows of stage "
+                           f"{stage} (got {tuple(x.shape)})")
+
+
+class _TemporalConvRaggedFn(torch.autograd.Function):
+    """_TemporalConvFn on the compact rows of one stage of a TimeSeriesMap."""
+
+    @staticmethod
+    def forward(ctx, x, tm, stage, nb, *params):
+        weights, biases = list(params[:nb]), list(params[nb:])
+        has_bias = biases[0] is not None
+        M, cin = x.shape
+        couts, tbs, _, _ = _branch_arrays(weights)
+        cout, taps = sum(couts), max(tbs)
+        y = torch.empty(M, cout, device=x.device, dtype=torch.float32)
+        d = C.byref(tm.desc)
+        if cin == 1 and nb == 1 and stage == 0:
+            check(LIB.hlhgat_tconv_embed_fwd_ragged(x.data_ptr(), d, weights[0].data_ptr(),
+                                                    _ptr(biases[0]), cout, taps, y.data_ptr(),
+                                                    _stream(x)), "tconv_embed_fwd_ragged")
+        else:
+            wp = _tconv_pack(weights, cin, taps, False)
+            bias = _tconv_bias(biases, couts, x.device) if has_bias else None
+            n1, n3 = _tconv_skip(couts, tbs, taps)
+            check(LIB.hlhgat_tconv_fwd_ragged(x.data_ptr(), d, stage, cin, wp.data_ptr(),
+                                              _ptr(bias), cout, taps, n1, n3, y.data_ptr(),
+                                              _stream(x)), "tconv_fwd_ragged")
+        ctx.tm, ctx.stage, ctx.nb, ctx.has_bias = tm, stage, nb, has_bias
+        ctx.save_for_backward(x, *weights)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, *weights = ctx.saved_tensors
+        tm, stage, nb = ctx.tm, ctx.stage, ctx.nb
+        M, cin = x.shape
+        couts, tbs, c_couts, c_tbs = _branch_arrays(weights)
+        cout, taps = sum(couts), max(tbs)
+        g = g.contiguous()
+        d = C.byref(tm.desc)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            wt = _tconv_pack(weights, cin, taps, True)
+            gx = torch.empty(M, cin, device=x.device, dtype=torch.float32)
+            check(LIB.hlhgat_tconv_fwd_ragged(g.data_ptr(), d, stage, cout, wt.data_ptr(), None,
+                                              cin, taps, 0, 0, gx.data_ptr(), _stream(x)),
+                  "tconv_bwd_data_ragged")
+        gws = [None] * nb
+        gbs = [None] * nb
+        if any(ctx.needs_input_grad[4:]):
+            gws = [torch.empty_like(w) for w in weights]
+            gb = (torch.empty(cout, device=x.device, dtype=torch.float32)
+                  if ctx.has_bias else None)
+            wsf = LIB.hlhgat_tconv_bwd_weight_workspace_floats(tm.n_series, tm.t_max[stage], cin,
+                                                               cout, taps)
+            ws = torch.empty(max(wsf, 1), device=x.device, dtype=torch.float32)
+            check(LIB.hlhgat_tconv_bwd_weight_ragged(
+                x.data_ptr(), g.data_ptr(), d, stage, cin, cout, taps, nb,
+                _arr(_lib.c_vp, [w.data_ptr() for w in gws]), c_couts, c_tbs, _ptr(gb),
+                ws.data_ptr(), wsf, _stream(x)), "tconv_bwd_weight_ragged")
+            if gb is not None:
+                gbs = list(torch.split(gb, couts))
+        return (gx, None, None, None, *gws, *gbs)
+
+
+def temporal_conv_ragged(x: torch.Tensor, tm: TimeSeriesMap, stage: int, weights,
+                         biases=None) -> torch.Tensor:
+    """temporal_conv on the compact rows x [capacity, Cin] of ``stage`` of a
+    TimeSeriesMap -> [capacity, sum Cout_b]: every series is padded with zeros
+    at its own two ends (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:501-509 on each
+    window alone); dead rows come out as zeros."""
+    if torch.is_tensor(weights):
+        weights = [weights]
+        biases = None if biases is None else [biases]
+    weights = list(weights)
+    nb = len(weights)
+    biases = [None] * nb if biases is None else list(biases)
+    _req_rows(x, tm, stage, "temporal_conv_ragged")
+    if len(biases) != nb or len({b is None for b in biases}) != 1:
+        raise RuntimeError("hlhgat: temporal_conv_ragged needs a bias for every branch or for none")
+    for w, b in zip(weights, biases):
+        _req_dev(w, "weight")
+        if w.dim() != 3 or w.size(1) != x.size(1):
+            raise RuntimeError(f"hlhgat: temporal_conv_ragged weight {tuple(w.shape)} for "
+                               f"{x.size(1)} input channels")
+        if b is not None:
+            _req_dev(b, "bias")
+    return _TemporalConvRaggedFn.apply(x.contiguous(), tm, int(stage), nb,
+                                       *[w.contiguous() for w in weights],
+                                       *[None if b is None else b.contiguous() for b in biases])
+
+
+class _LeakyMaxPoolTimeRaggedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, tm, slope):
+        Cc = x.size(1)
+        y = torch.empty(tm.capacity(1), Cc, device=x.device, dtype=torch.float32)
+        idx = torch.empty(tm.capacity(1), Cc, device=x.device, dtype=torch.int32)
+        check(LIB.hlhgat_leaky_maxpool_time_fwd_ragged(x.data_ptr(), C.byref(tm.desc), Cc, slope,
+                                                       y.data_ptr(), idx.data_ptr(), _stream(x)),
+              "leaky_maxpool_time_fwd_ragged")
+        ctx.tm, ctx.slope = tm, slope
+        ctx.save_for_backward(x, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, idx = ctx.saved_tensors
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        check(LIB.hlhgat_leaky_maxpool_time_bwd_ragged(x.data_ptr(), g.data_ptr(), idx.data_ptr(),
+                                                       C.byref(ctx.tm.desc), x.size(1), ctx.slope,
+                                                       gx.data_ptr(), _stream(x)),
+              "leaky_maxpool_time_bwd_ragged")
+        return gx, None, None
+
+
+def leaky_maxpool_time_ragged(x: torch.Tensor, tm: TimeSeriesMap, slope: float) -> torch.Tensor:
+    """leaky_maxpool_time with the map's window on the compact stage-0 rows
+    x [capacity_0, C] -> compact stage-1 rows [capacity_1, C]: every series
+    pooled over its own length (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:488, :505)."""
+    _req_rows(x, tm, 0, "leaky_maxpool_time_ragged")
+    return _LeakyMaxPoolTimeRaggedFn.apply(x.contiguous(), tm, float(slope))
+
+
+class _TimeReadoutRaggedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, tm, slope):
+        Cc = x.size(1)
+        y = torch.empty(tm.n_series, 2 * Cc, device=x.device, dtype=torch.float32)
+        idx = torch.empty(tm.n_series, Cc, device=x.device, dtype=torch.int32)
+        check(LIB.hlhgat_time_readout_fwd_ragged(x.data_ptr(), C.byref(tm.desc), Cc, slope,
+                                                 y.data_ptr(), idx.data_ptr(), _stream(x)),
+              "time_readout_fwd_ragged")
+        ctx.tm, ctx.slope = tm, slope
+        ctx.save_for_backward(x, idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, idx = ctx.saved_tensors
+        g = g.contiguous()
+        gx = torch.empty_like(x)
+        check(LIB.hlhgat_time_readout_bwd_ragged(x.data_ptr(), g.data_ptr(), idx.data_ptr(),
+                                                 C.byref(ctx.tm.desc), x.size(1), ctx.slope,
+                                                 gx.data_ptr(), _stream(x)),
+              "time_readout_bwd_ragged")
+        return gx, None, None
+
+
+def time_readout_ragged(x: torch.Tensor, tm: TimeSeriesMap, slope: float) -> torch.Tensor:
+    """time_readout on the compact stage-1 rows x [capacity_1, C] -> [S, 2C]:
+    the maximum and the mean over every series' own length
+    (HL-HGAT-DEMO/lib/Hodge_Cheb_Conv.py:509-513)."""
+    _req_rows(x, tm, 1, "time_readout_ragged")
+    return _TimeReadoutRaggedFn.apply(x.contiguous(), tm, float(slope))
 
 
 # ----------------------------------------------------------------------------
@@ -3186,7 +3444,8 @@ class FcPrepared:
 def fc_prepare(x: torch.Tensor, n_graphs: int, window=None, want_z: bool = True, *,
                n_nodes: Optional[int] = None, graph_rows: Optional[torch.Tensor] = None,
                workspace: Optional[torch.Tensor] = None,
-               z: Optional[torch.Tensor] = None) -> FcPrepared:
+               z: Optional[torch.Tensor] = None, windows=None,
+               t_max: Optional[int] = None) -> FcPrepared:
     """The row pass of Brain_MLGC_ALL.get for n_graphs subjects at once
     (HL-HGAT-DEMO/lib/Hodge_Dataset.py:136): x is [n_graphs * N, T_all] (rows
     may be strided), graph g owning rows [g N, (g + 1) N); window = (t0, T)
@@ -3197,7 +3456,12 @@ def fc_prepare(x: torch.Tensor, n_graphs: int, window=None, want_z: bool = True,
     picks graph g's rows from row graph_rows[g] of a larger x; its values are
     the caller's to bound.  workspace: a uint8 tensor of at least
     hlhgat_fc_workspace_bytes to reuse; z: a contiguous [n_graphs * N, T]
-    tensor to fill (want_z).  Not differentiable: these are inputs."""
+    tensor to fill (want_z).  windows = (t0, len), two contiguous int32
+    [n_graphs] device tensors, with t_max (default: every column of x) gives
+    every graph its own window [t0[g], t0[g] + len[g]), 2 <= len[g] <= t_max
+    (the per-sample crop of :131-135): statistics over the graph's own window,
+    z [n_graphs * N, t_max] with zeros past len[g], and an FcPrepared of
+    T = t_max.  Not differentiable: these are inputs."""
     _req_dev(x, "x")
     if x.dim() != 2:
         raise RuntimeError(f"hlhgat: fc_prepare wants x [rows, T], got {tuple(x.shape)}")
@@ -3218,7 +3482,18 @@ def fc_prepare(x: torch.Tensor, n_graphs: int, window=None, want_z: bool = True,
         if graph_rows.numel() != G or not graph_rows.is_contiguous() or N > x.size(0):
             raise RuntimeError(f"hlhgat: fc_prepare: graph_rows must be contiguous int64 [{G}] and "
                                f"n_nodes <= {x.size(0)} rows")
-    t0, T = (0, x.size(1)) if window is None else (int(window[0]), int(window[1]))
+    if windows is not None:
+        if window is not None:
+            raise RuntimeError("hlhgat: fc_prepare takes window or windows, not both")
+        w0, wl = windows
+        for t, name in ((w0, "windows[0]"), (wl, "windows[1]")):
+            _req_dev(t, name, torch.int32)
+            if t.numel() != G or not t.is_contiguous() or t.device != x.device:
+                raise RuntimeError(f"hlhgat: fc_prepare: {name} must be contiguous int32 [{G}] on "
+                                   f"{x.device}")
+        t0, T = 0, int(x.size(1) if t_max is None else t_max)
+    else:
+        t0, T = (0, x.size(1)) if window is None else (int(window[0]), int(window[1]))
     if t0 < 0 or t0 + T > x.size(1):
         raise RuntimeError(f"hlhgat: fc_prepare: window [{t0}, {t0 + T}) outside the {x.size(1)} "
                            f"columns of x")
@@ -3238,6 +3513,12 @@ def fc_prepare(x: torch.Tensor, n_graphs: int, window=None, want_z: bool = True,
         if tuple(z.shape) != (G * N, T) or not z.is_contiguous() or z.device != x.device:
             raise RuntimeError(f"hlhgat: fc_prepare: z must be contiguous [{G * N}, {T}] on "
                                f"{x.device}")
+    if windows is not None:
+        check(LIB.hlhgat_fc_prepare_windows(x.data_ptr(), _ld(x), _ptr(graph_rows), G, N,
+                                            windows[0].data_ptr(), windows[1].data_ptr(), T,
+                                            _ptr(z), workspace.data_ptr(), workspace.numel(),
+                                            _stream(x)), "fc_prepare_windows")
+        return FcPrepared(workspace, G, N, T, z)
     check(LIB.hlhgat_fc_prepare(x.data_ptr(), _ld(x), _ptr(graph_rows), G, N, t0, T, _ptr(z),
                                 workspace.data_ptr(), workspace.numel(), _stream(x)),
           "fc_prepare")
@@ -3355,6 +3636,9 @@ _DEVERR_TEXT = {
     _lib.DEVERR_MLGC_RANGE: "mlgc_device: an edge end outside its graph's node range, a perm "
                             "entry outside [0, n) or graph offsets that leave the arrays; the "
                             "offender was treated as absent",
+    _lib.DEVERR_TSERIES_LEN: "time_series_map / fc_prepare(windows=): a series length outside "
+                             "[1, t_max] or a window that leaves its row; it was clamped into "
+                             "range",
 }
 
 

@@ -505,7 +505,13 @@ class BrainPipeline:
       * window="random" draws t_begin in [0, 75) and a length in [250, 300)
         ONCE PER BATCH from `seed`; the reference draws them per sample
         (:131-133), which its own collation cannot batch when the lengths
-        differ (x_t rows of different widths);
+        differ (x_t rows of different widths).  window="per_sample" is the
+        reference's draw, one (t_begin, length) per subject: x_t is then
+        padded to [B N, t_max] (zeros past a subject's own length), level 0
+        carries t_len (int32 [B N], each time course's length) and
+        Inception1D runs its ragged path on it.  t_max = min(299, the
+        shortest series of the pipeline) whatever was drawn, so every batch
+        of one size has one shape -- one captured graph under TrainStep;
       * a region whose series is constant over the window gets NaN on its
         edges (the exact 0 / 0); the reference's float result there is
         rounding noise.
@@ -593,6 +599,85 @@ class BrainPipeline:
             self._levels[key] = out
         return out
 
+    T_MAX = 299  # the longest window Brain_MLGC_ALL.get draws (:132)
+
+    @property
+    def t_max(self) -> int:
+        """The padded width of x_t under per-sample windows."""
+        return min(self.T_MAX, int(self.lens.min()))
+
+    def _windows(self, idx, window, seed) -> np.ndarray:
+        """Per-subject (t0, len) as int64 [B, 2]: drawn from `seed` as
+        Brain_MLGC_ALL.get draws them (:131-133), or the caller's array."""
+        lens = self.lens[idx]
+        if isinstance(window, str):
+            rng = np.random.default_rng(seed)
+            w = np.stack([rng.integers(0, 75, size=idx.size),
+                          rng.integers(250, 300, size=idx.size)], 1).astype(np.int64)
+            # a slice past the series end is cut, as in the reference; the
+            # padded width bounds it when the series differ in length
+            w[:, 1] = np.minimum(np.minimum(w[:, 1], lens - w[:, 0]), self.t_max)
+        else:
+            w = np.asarray(window)
+            if w.shape != (idx.size, 2) or not np.issubdtype(w.dtype, np.integer):
+                raise ValueError(f"BrainPipeline: per-sample windows must be an int array "
+                                 f"[{idx.size}, 2] of (t0, len), got {w.dtype} {w.shape}")
+            w = w.astype(np.int64)
+        if (w[:, 0] < 0).any() or (w[:, 1] < 2).any() or (w.sum(1) > lens).any() or \
+                (w[:, 1] > self.t_max).any():
+            raise ValueError(f"BrainPipeline: windows {w.tolist()} do not fit series of lengths "
+                             f"{lens.tolist()} with 2 <= len <= t_max = {self.t_max}")
+        return w
+
+    def _batch_per_sample(self, idx, w, dev, levels, lv0):
+        B, N, t_max = idx.size, self.N, self.t_max
+        if dev.type == "cpu":
+            xs_t, xs_s = [], []
+            ei = self.edge_index
+            for i, (t0, n) in zip(idx, w.tolist()):
+                f = self.series[i][:, t0:t0 + n]
+                f = (f - f.mean()) / f.std()
+                xs_t.append(torch.nn.functional.pad(f, (0, t_max - n)))
+                xs_s.append(torch.corrcoef(f)[ei[0], ei[1]].view(-1, 1))
+            lv0.x_t, lv0.x_s = torch.cat(xs_t), torch.cat(xs_s)
+            lv0.t_len = torch.from_numpy(np.repeat(w[:, 1], N).astype(np.int32))
+            lv0.y = self.targets[torch.from_numpy(idx)]
+            return [lv0] + list(levels[1:])
+        from . import ops
+        st = self._device_state(dev)
+        ids = _h2d(np.concatenate([idx, idx * N, w[:, 0], w[:, 1]]), dev)
+        win = ids[2 * B:].to(torch.int32)
+        x, rows = self._batch_rows(st, idx, ids, dev)
+        prep = ops.fc_prepare(x, B, n_nodes=N, graph_rows=rows, workspace=self._batch_ws(st, B, dev),
+                              windows=(win[:B], win[B:]), t_max=t_max)
+        lv0.x_t = prep.z
+        lv0.t_len = win[B:].repeat_interleave(N)
+        lv0.x_s = ops.fc_edges(prep, st["pair2edge"], self.E, tiles=st["tiles"])
+        lv0.y = st["targets"].index_select(0, ids[:B])
+        return [lv0] + list(levels[1:])
+
+    def _batch_rows(self, st, idx, ids, dev):
+        """(x, graph_rows) of a batch: the resident block and the subjects'
+        first rows, or the batch's rows staged from the pinned block."""
+        B = idx.size
+        if self.resident:
+            return st["block"], ids[B:2 * B]
+        blk = self._host_block(pin=True)
+        x = st["stage"].get(B)
+        if x is None:
+            x = st["stage"][B] = torch.empty((B * self.N, blk.shape[2]), device=dev)
+        for b, i in enumerate(idx):
+            x[b * self.N:(b + 1) * self.N].copy_(blk[i], non_blocking=True)
+        return x, None
+
+    def _batch_ws(self, st, B, dev):
+        from . import _lib
+        ws = st["ws"].get(B)
+        if ws is None:
+            need = int(_lib.LIB.hlhgat_fc_workspace_bytes(B, self.N, int(self.lens.max())))
+            ws = st["ws"][B] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
     def _window(self, idx, window, seed):
         lens = self.lens[idx]
         if window is None:
@@ -618,17 +703,21 @@ class BrainPipeline:
     def batch(self, idx, window=None, seed: int = 0, device="cuda") -> List[Batch]:
         """The level list of subjects idx: the cached collation of len(idx)
         copies with x_t [B N, T], x_s [B E, 1] and y [B] of level 0 set.
-        window: None (the whole series), (t0, T), or "random" (see the class
-        docstring: one draw per batch)."""
+        window: None (the whole series), (t0, T), "random" (one draw per
+        batch), "per_sample" (one draw per subject, as the reference) or an
+        int array [B, 2] of per-subject (t0, len); the last two give x_t
+        [B N, t_max] with t_len (see the class docstring)."""
         import copy
         idx = np.asarray([int(i) for i in idx], dtype=np.int64)
         B = idx.size
         if B == 0 or idx.min() < 0 or idx.max() >= len(self.series):
             raise ValueError(f"BrainPipeline: subjects {idx.tolist()} outside [0, {len(self)})")
-        t0, T = self._window(idx, window, seed)
         dev = torch.device(device)
         levels = self.levels_for(B, dev)
         lv0 = copy.copy(levels[0])  # the same structure tensors, three fields of its own
+        if (isinstance(window, str) and window == "per_sample") or np.ndim(window) == 2:
+            return self._batch_per_sample(idx, self._windows(idx, window, seed), dev, levels, lv0)
+        t0, T = self._window(idx, window, seed)
         if dev.type == "cpu":
             xs_t, xs_s = [], []
             ei = self.edge_index
@@ -643,22 +732,9 @@ class BrainPipeline:
         from . import _lib, ops
         st = self._device_state(dev)
         ids = _h2d(np.concatenate([idx, idx * self.N]), dev)
-        if self.resident:
-            x, rows = st["block"], ids[B:]
-        else:  # the batch's rows only, from the pinned block into a reused buffer
-            blk = self._host_block(pin=True)
-            x = st["stage"].get(B)
-            if x is None:
-                x = st["stage"][B] = torch.empty((B * self.N, blk.shape[2]), device=dev)
-            for b, i in enumerate(idx):
-                x[b * self.N:(b + 1) * self.N].copy_(blk[i], non_blocking=True)
-            rows = None
-        ws = st["ws"].get(B)
-        if ws is None:
-            need = int(_lib.LIB.hlhgat_fc_workspace_bytes(B, self.N, int(self.lens.max())))
-            ws = st["ws"][B] = torch.empty(need, dtype=torch.uint8, device=dev)
+        x, rows = self._batch_rows(st, idx, ids, dev)
         prep = ops.fc_prepare(x, B, window=(t0, T), n_nodes=self.N, graph_rows=rows,
-                              workspace=ws)
+                              workspace=self._batch_ws(st, B, dev))
         lv0.x_t = prep.z
         lv0.x_s = ops.fc_edges(prep, st["pair2edge"], self.E, tiles=st["tiles"])
         lv0.y = st["targets"].index_select(0, ids[:B])

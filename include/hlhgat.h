@@ -1197,6 +1197,10 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
  * outside [0, n), or graph offsets that leave the arrays / the workspace; the
  * offender was treated as absent */
 #define HLHGAT_DEVERR_MLGC_RANGE 64u
+/* hlhgat_tseries_map: a series length outside [1, t_max], or
+ * hlhgat_fc_prepare_windows: a window that is shorter than two samples, longer
+ * than t_max or leaves the row; the offender was clamped into range */
+#define HLHGAT_DEVERR_TSERIES_LEN 128u
 int hlhgat_device_errors(unsigned* out);
 int hlhgat_clear_device_errors(void);
 
@@ -1326,6 +1330,84 @@ int hlhgat_time_readout_fwd(const float* x, int64_t n, int64_t t, int64_t c, flo
                             float* y, int32_t* idx, void* stream);
 int hlhgat_time_readout_bwd(const float* x, const float* dy, const int32_t* idx, int64_t n,
                             int64_t t, int64_t c, float slope, float* dx, void* stream);
+
+/* ---- ragged time layout: series of different lengths in one batch -------- */
+/* Brain_MLGC_ALL.get (HL-HGAT-DEMO/lib/Hodge_Dataset.py:131-133) crops every
+ * sample to its own window, t_begin in [0, 75) and a length in [250, 300); the
+ * reference then runs Inception1D one batch = one length, because rows of
+ * different widths do not collate.  Channels-last activations do: series s
+ * owns rows [soff[s], soff[s] + len[s]) of a buffer of n_series * t_max rows
+ * (a fixed capacity, so no shape depends on the lengths); rows from
+ * n_rows = sum len on are dead.  Stage 0 is the layout before the max-pool
+ * (lengths len[s], capacity per series t_max[0]), stage 1 the one after it
+ * (hlhgat_maxpool_time_len(len[s], pool) and t_max[1] =
+ * hlhgat_maxpool_time_len(t_max[0], pool)).  All tables live on the device:
+ *   soff[i]  int32 [n_series + 1]  series offsets (soff[i][n_series] = n_rows[i])
+ *   tab[i]   int32 [capacity_i][2] per row (step within its series, series
+ *                                  length); (0, 0) on a dead row
+ *   sid[i]   int32 [capacity_i]    per row its series (0 on a dead row)
+ *   n_rows   int32 [2]             the valid-row prefix of either stage: the
+ *                                  n_valid of the BatchNorm entries
+ * Every *_ragged entry is its dense twin (same tiles, staging, tap skipping,
+ * chunking and reduction order: bit for bit the dense result when every
+ * length is t_max) with the position predicate read from tab instead of
+ * row % T; it never reads an input row >= n_rows and writes zeros to every
+ * output row >= n_rows.  Per series the arithmetic is the reference's on that
+ * series alone: zero padding at the window's own two ends (:483-492), the
+ * pool length of its own length (:488), the mean over its own length (:512). */
+typedef struct {
+  int64_t n_series;
+  int64_t t_max[2];
+  int32_t pool; /* the max-pool window m (stride m - 1, padding (m - 1) / 2) */
+  int32_t* soff[2];
+  int32_t* tab[2];
+  int32_t* sid[2];
+  int32_t* n_rows;
+} hlhgat_tseries_t;
+
+/* Fills every table of `map` from tlen (int32 [n_series], device), in two
+ * launches and without a host read: the lengths the reference draws at
+ * lib/Hodge_Dataset.py:131-133.  A length outside [1, t_max[0]] is clamped
+ * into it and raises HLHGAT_DEVERR_TSERIES_LEN. */
+int hlhgat_tseries_map(const int32_t* tlen, const hlhgat_tseries_t* map, void* stream);
+/* inverse = 0: the padded time courses src [n_series, ldx] (x[s][len[s]:] is
+ * never read) as the compact stage-0 column dst [capacity_0] -- the
+ * torch.unsqueeze(x, 1) of lib/Hodge_Cheb_Conv.py:500 on every window at once;
+ * inverse = 1: its gradient, compact src -> padded dst, zeros past len[s]. */
+int hlhgat_tseries_pack(const float* src, int64_t ldx, const hlhgat_tseries_t* map, int inverse,
+                        float* dst, void* stream);
+/* hlhgat_tconv_fwd (:502-504, :506-508, and its data gradient) on the rows of
+ * `stage`: x [capacity, cin] -> y [capacity, cout]. */
+int hlhgat_tconv_fwd_ragged(const float* x, const hlhgat_tseries_t* map, int stage, int64_t cin,
+                            const float* wp, const float* bias, int64_t cout, int taps,
+                            int64_t n1, int64_t n3, float* y, void* stream);
+/* hlhgat_tconv_embed_fwd (:483, :501) on the compact stage-0 column x. */
+int hlhgat_tconv_embed_fwd_ragged(const float* x, const hlhgat_tseries_t* map, const float* w,
+                                  const float* bias, int64_t c, int taps, float* y,
+                                  void* stream);
+/* hlhgat_tconv_bwd_weight (the autograd of :501-508) on the rows of `stage`;
+ * the workspace is that of (n_series, t_max[stage]).  The partial-sum slot of
+ * a row chunk past n_rows is written as zeros, so the reduction is the dense
+ * one. */
+int hlhgat_tconv_bwd_weight_ragged(const float* x, const float* dy, const hlhgat_tseries_t* map,
+                                   int stage, int64_t cin, int64_t cout, int taps, int nb,
+                                   float* const* dw, const int64_t* cout_b,
+                                   const int32_t* taps_b, float* dbias, float* workspace,
+                                   int64_t workspace_floats, void* stream);
+/* hlhgat_leaky_maxpool_time_fwd / _bwd (:488, :505): stage-0 rows in, stage-1
+ * rows out, idx the step within the series. */
+int hlhgat_leaky_maxpool_time_fwd_ragged(const float* x, const hlhgat_tseries_t* map, int64_t c,
+                                         float slope, float* y, int32_t* idx, void* stream);
+int hlhgat_leaky_maxpool_time_bwd_ragged(const float* x, const float* dy, const int32_t* idx,
+                                         const hlhgat_tseries_t* map, int64_t c, float slope,
+                                         float* dx, void* stream);
+/* hlhgat_time_readout_fwd / _bwd (:509-513) on the stage-1 rows: y
+ * [n_series, 2c], the mean divided by the series' own length. */
+int hlhgat_time_readout_fwd_ragged(const float* x, const hlhgat_tseries_t* map, int64_t c,
+                                   float slope, float* y, int32_t* idx, void* stream);
+int hlhgat_time_readout_bwd_ragged(const float* x, const float* dy, const int32_t* idx,
+                                   const hlhgat_tseries_t* map, int64_t c, float slope,
+                                   float* dx, void* stream);
 
 /* ---- training-mode feature dropout -------------------------------------- */
 /* Dropout(p=dropout_ratio), the tail of every HL block (lib/Hodge_ST_Model.py:
@@ -1470,6 +1552,21 @@ size_t hlhgat_fc_workspace_bytes(int64_t G, int64_t N, int64_t T);
 int hlhgat_fc_prepare(const float* x, int64_t ldx, const int64_t* graph_rows, int64_t G,
                       int64_t N, int64_t t0, int64_t T, float* z, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* hlhgat_fc_prepare with a window per graph, the per-sample crop of
+ * Brain_MLGC_ALL.get (lib/Hodge_Dataset.py:131-135: f = f[:, t_begin:t_begin +
+ * length], then the z-score and corrcoef of that window): graph g reads
+ * columns [t0[g], t0[g] + len[g]) (int32 [G], device), 2 <= len[g] <= t_max
+ * and the window inside the ldx columns; a window outside that is clamped
+ * into it and raises HLHGAT_DEVERR_TSERIES_LEN.  Mean and unbiased std over
+ * the graph's own N x len[g] elements; z is [G*N, t_max] with zeros past
+ * len[g], and the workspace rows are zero-padded to t_max, so hlhgat_fc_dense
+ * / hlhgat_fc_edges run on it with T = t_max (workspace bytes: those of
+ * T = t_max).  Same fp64 fixed-order accumulators: graph g's values are bit
+ * for bit those of hlhgat_fc_prepare on that graph alone with (t0[g],
+ * len[g]). */
+int hlhgat_fc_prepare_windows(const float* x, int64_t ldx, const int64_t* graph_rows, int64_t G,
+                              int64_t N, const int32_t* t0, const int32_t* len, int64_t t_max,
+                              float* z, void* workspace, size_t workspace_bytes, void* stream);
 /* fc[G, N, N] = torch.corrcoef of every graph's window (:137 before the
  * indexing; the FC stack of FC2mask, :148-153) from a prepared workspace:
  * fp32 MFMA on 64 x 64 tiles with row tile <= column tile, each value stored

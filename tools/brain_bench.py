@@ -28,6 +28,17 @@
     (median of 20 after 5 warm-up steps), and the replayed step's copy of the
     batch into the graph's static buffers (_Captured.load) on its own.
 
+(f) --per-sample-windows, a run of its own (profiles/brain_ragged.json):
+    per-sample fMRI windows.  Inception1D at N = 1340 on its
+    ragged path with every length 275 against the dense path at T = 275, and
+    with lengths drawn in [250, 300) at t_max = 299 against the dense path at
+    T = 299: forward and forward + backward, the modes alternated in one
+    process, median of --reps.  Then the first --aug-steps augmented training
+    steps of (e)'s model at 5 subjects, captures included, wall time:
+    window="random" (a graph per drawn length) against window="per_sample"
+    (one graph), with the graphs captured and the bytes their static batches
+    hold.
+
 Event timing after warm-up, median of --reps runs.
 """
 from __future__ import annotations
@@ -386,6 +397,101 @@ def train_step(reps=20, warmup=5):
     return res
 
 
+def _alternated(fns, reps, warmup=3):
+    """Median event ms of every fn, the fns taking turns inside one loop."""
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, f in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return {k: round(float(np.median(v)), 4) for k, v in ms.items()}
+
+
+def ragged_front_end(reps):
+    """(f), kernel cost: ragged against dense Inception1D, alternated."""
+    import hlhgat
+    from hlhgat import ops
+    dev = torch.device("cuda:0")
+    mod = hlhgat.Inception1D(C, NC, MP, if_readout=True).to(dev).train()
+    rng = np.random.default_rng(0)
+    out = {}
+    for name, t_max, lens in (("equal_275", 275, np.full(N, 275)),
+                              ("drawn_250_300", 299, rng.integers(250, 300, size=N))):
+        x = torch.randn(N, t_max, device=dev)
+        ln = torch.from_numpy(lens.astype(np.int32)).to(dev)
+
+        def run(lengths, grad):
+            if not grad:
+                with torch.no_grad():
+                    return mod(x, lengths)
+            for p in mod.parameters():
+                p.grad = None
+            mod(x, lengths).sum().backward()
+
+        ms = _alternated({"dense_fwd": lambda: run(None, False), "ragged_fwd": lambda: run(ln, False),
+                          "dense_fwd_bwd": lambda: run(None, True),
+                          "ragged_fwd_bwd": lambda: run(ln, True)}, reps)
+        ms["t_max"], ms["dead_row_share"] = t_max, round(1.0 - float(lens.sum()) / (N * t_max), 4)
+        ms["ratio_fwd"] = round(ms["ragged_fwd"] / ms["dense_fwd"], 4)
+        ms["ratio_fwd_bwd"] = round(ms["ragged_fwd_bwd"] / ms["dense_fwd_bwd"], 4)
+        out[name] = ms
+    ops.check_device_errors()
+    return out
+
+
+def augmented_replay(steps):
+    """(f), replay under augmentation: the first `steps` training steps."""
+    import hlhgat
+    from hlhgat import ops
+    from hlhgat.train import TrainStep
+    dev = torch.device("cuda:0")
+    B, S = 5, 10
+    fine, coarse, c_node, c_edge = skeleton_levels()
+    fine.pos_t, fine.pos_s = c_node.view(-1), c_edge.view(-1)
+    n1, E1 = int(coarse.num_node1), int(coarse.num_edge1)
+    rng = np.random.default_rng(0)
+    n = int(fine.num_node1)
+    series = [((rng.standard_normal((n, 6)) @ rng.standard_normal((6, T))
+                + rng.standard_normal((n, T))) * 50 + 1000).astype(np.float32) for _ in range(S)]
+    pipe = hlhgat.BrainPipeline(series, rng.standard_normal(S).astype(np.float32), [fine, coarse])
+    mse = hlhgat.nn.MSELoss()
+    res = {"graphs": B, "steps": steps}
+    for window in ("random", "per_sample"):
+        torch.manual_seed(0)
+        m = hlhgat.HL_HGAT_attpool(channels=[2, 2, 2], filters=[32, 64, 128], mlp_channels=[],
+                                   K=4, pool_num=1, num_nodepedge=n1 + E1).to(dev).train()
+        step = TrainStep(m, lambda o, d: mse(o[0], d[0].y.view(-1, 1)), lr=1e-4,
+                         weight_decay=1e-4, graphs=True)
+        pipe.batch(range(B), window=window, seed=0, device=dev)  # the level list is collated
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(steps):
+            loss = step(pipe.batch([(k * B + j) % S for j in range(B)], window=window, seed=k,
+                                   device=dev))
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        held = sum(v.numel() * v.element_size() for ent in step._graphs.values()
+                   for b in (ent.batch if isinstance(ent.batch, (list, tuple)) else [ent.batch])
+                   for v in vars(b).values() if torch.is_tensor(v))
+        res[window] = {"wall_s": round(wall, 3), "ms_per_step": round(wall * 1e3 / steps, 3),
+                       "graphs_captured": int(step.stats["captures"]),
+                       "graphs_held": len(step._graphs),
+                       "static_batch_mbytes": round(held / 1e6, 1),
+                       "stats": dict(step.stats), "last_loss": float(loss)}
+        ops.check_device_errors()
+        del step, m
+        torch.cuda.empty_cache()
+    return res
+
+
 def torch_child(args, res):
     """Last GPU step of the run: torch's own ops in a child with a time limit."""
     t0 = time.time()
@@ -423,7 +529,22 @@ def main():
                          "--train-out")
     ap.add_argument("--train-out", default=os.path.join(REPO, "profiles",
                                                         "brain_train_step.json"))
+    ap.add_argument("--per-sample-windows", action="store_true",
+                    help="the ragged front end against the dense one and the first augmented "
+                         "training steps, written to --ragged-out")
+    ap.add_argument("--ragged-out", default=os.path.join(REPO, "profiles", "brain_ragged.json"))
+    ap.add_argument("--aug-steps", type=int, default=200)
     args = ap.parse_args()
+    if args.per_sample_windows:
+        res = {"shape": {"N": N, "in_channels": C, "num_channels": NC, "maxpool": MP},
+               "reps": args.reps, "front_end": ragged_front_end(args.reps)}
+        if args.aug_steps > 0:
+            res["augmented_replay"] = augmented_replay(args.aug_steps)
+        os.makedirs(os.path.dirname(args.ragged_out), exist_ok=True)
+        with open(args.ragged_out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if args.train_step:
         res = train_step()
         os.makedirs(os.path.dirname(args.train_out), exist_ok=True)
