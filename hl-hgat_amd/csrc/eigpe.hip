@@ -31,6 +31,9 @@
 //
 // Eigenvectors are defined up to sign (and, inside a cluster of equal
 // eigenvalues, up to rotation); the reference flips PE signs at random anyway.
+//
+// The same solver over the edge operator y = B1^T (B1 x) gives the molecular
+// datasets' eig_pe(L1) (hlhgat_eig_pe_edges, at the end of this file).
 #include "common.h"
 #include "tridiag.h"
 
@@ -52,6 +55,7 @@ struct EigArgs {
   const int64_t* ei;  // [2][n_edges]
   int64_t n_edges;
   const int64_t* node_ptr;
+  const int64_t* edge_ptr;  // [n_graphs + 1], the edge entry only (edges grouped by graph)
   int k;
   float* pe;
   int64_t ldpe;
@@ -101,6 +105,7 @@ struct Work {
   double* lu;   // [kEpSolvers][5][n] LU factors + pivots of T - lambda I
   int* rp;      // [n + 1] local adjacency (LDS layout only)
   int* nb;      // [2 E]
+  int* en;      // [2 E] local ends of each edge (edge operator, LDS layout only)
   int ldq;
 };
 
@@ -111,7 +116,15 @@ __device__ __forceinline__ int64_t small_bytes(int n, int nnz, int k) {
          4 * ((int64_t)n + 1 + nnz);
 }
 
-__device__ __forceinline__ Work carve(char* p, int n, int k, bool adjacency) {
+// The edge operator's LDS layout: the same doubles at dimension n = E_g, the
+// node CSR of the graph's nv nodes (2 E_g signed entries) and the local ends.
+__device__ __forceinline__ int64_t small_bytes_edges(int n, int nv, int k) {
+  return small_bytes(n, 0, k) - 4 * ((int64_t)n + 1) + 4 * ((int64_t)nv + 1 + 4ll * n);
+}
+
+// nrp = rows of the adjacency (n for the node operator, the graph's node
+// count for the edge operator, whose n counts edges)
+__device__ __forceinline__ Work carve(char* p, int n, int k, bool adjacency, int nrp) {
   Work W;
   W.ldq = n + 1;
   double* d = reinterpret_cast<double*>(p);
@@ -132,7 +145,8 @@ __device__ __forceinline__ Work carve(char* p, int n, int k, bool adjacency) {
   W.lu = d;
   d += (int64_t)kEpSolvers * 5 * n;
   W.rp = adjacency ? reinterpret_cast<int*>(d) : nullptr;
-  W.nb = adjacency ? W.rp + n + 1 : nullptr;
+  W.nb = adjacency ? W.rp + nrp + 1 : nullptr;
+  W.en = nullptr;
   return W;
 }
 
@@ -285,15 +299,39 @@ __device__ __forceinline__ void inverse_iteration(const double* al, const double
   }
 }
 
-template <bool SMALL>
+// EDGE = false: the node operator L0 on the graph's n nodes from n0.
+// EDGE = true: the edge operator L1 = B1^T B1 on the graph's n edges from e0g
+// (its nv nodes from n0); the output rows are the edge rows and lambda_max is
+// not written.  Everything after the operator is the same code.
+template <bool SMALL, bool EDGE>
 __device__ __forceinline__ void eig_pe_graph(const EigArgs& a, int g, int64_t n0, int n, char* base, double* red,
-                             double* lam, int* clus) {
+                             double* lam, int* clus, int64_t e0g = 0, int nv = 0) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int k = a.k;
   const int ebase = a.inc_rowptr[n0];
-  const int nnz = a.inc_rowptr[n0 + n] - ebase;
-  Work W = carve(base, n, k, SMALL);
-  if (SMALL) {
+  const int nnz = a.inc_rowptr[n0 + (EDGE ? nv : n)] - ebase;
+  Work W = carve(base, n, k, SMALL, EDGE ? nv : n);
+  if (SMALL && EDGE) {
+    // the caller took this path only with nnz == 2 n; ids are clamped so that
+    // an edge list that is not grouped as edge_ptr says cannot leave the LDS
+    W.en = W.nb + 2 * n;
+    for (int v = tid; v <= nv; v += kEpThreads) W.rp[v] = a.inc_rowptr[n0 + v] - ebase;
+    for (int v = tid; v < nv; v += kEpThreads) {
+      const int p0 = a.inc_rowptr[n0 + v], p1 = a.inc_rowptr[n0 + v + 1];
+      for (int p = p0; p < p1; ++p) {
+        const int64_t e = a.inc_edge[p];
+        int64_t f = e - e0g;
+        f = f < 0 ? 0 : (f >= n ? n - 1 : f);
+        // bit 0: this node is the edge's second end (B1 = +1 there, -1 at the first)
+        W.nb[p - ebase] = (int)(f << 1) | (a.ei[a.n_edges + e] == n0 + v ? 1 : 0);
+      }
+    }
+    for (int e = tid; e < n; e += kEpThreads) {
+      int64_t i = a.ei[e0g + e] - n0, j = a.ei[a.n_edges + e0g + e] - n0;
+      W.en[2 * e] = (int)(i < 0 ? 0 : (i >= nv ? nv - 1 : i));
+      W.en[2 * e + 1] = (int)(j < 0 ? 0 : (j >= nv ? nv - 1 : j));
+    }
+  } else if (SMALL) {
     for (int v = tid; v <= n; v += kEpThreads) W.rp[v] = a.inc_rowptr[n0 + v] - ebase;
     for (int v = tid; v < n; v += kEpThreads) {
       const int e0 = a.inc_rowptr[n0 + v], e1 = a.inc_rowptr[n0 + v + 1];
@@ -305,10 +343,40 @@ __device__ __forceinline__ void eig_pe_graph(const EigArgs& a, int g, int64_t n0
     }
   }
   (void)nnz;
-  auto apply = [&](const double* x, double* y) {  // y = L0 x
+  auto apply = [&](const double* x, double* y) {  // y = L0 x (EDGE: y = B1^T (B1 x))
     for (int v = tid; v < n; v += kEpThreads) {
       double s;
-      if (SMALL) {
+      if constexpr (EDGE) {
+        // (B1 x) at the edge's second end minus (B1 x) at its first, each
+        // summed over that node's incident edges in CSR order
+        double tj = 0.0, ti = 0.0;
+        if (SMALL) {
+          const int i = W.en[2 * v], j = W.en[2 * v + 1];
+          for (int p = W.rp[j]; p < W.rp[j + 1]; ++p) {
+            const int c = W.nb[p];
+            tj += (c & 1) ? x[c >> 1] : -x[c >> 1];
+          }
+          for (int p = W.rp[i]; p < W.rp[i + 1]; ++p) {
+            const int c = W.nb[p];
+            ti += (c & 1) ? x[c >> 1] : -x[c >> 1];
+          }
+        } else {
+          const int64_t i = a.ei[e0g + v], j = a.ei[a.n_edges + e0g + v];
+          for (int p = a.inc_rowptr[j]; p < a.inc_rowptr[j + 1]; ++p) {
+            const int64_t e = a.inc_edge[p];
+            const uint64_t f = (uint64_t)(e - e0g);
+            const double xf = f < (uint64_t)n ? x[f] : 0.0;
+            tj += a.ei[a.n_edges + e] == j ? xf : -xf;
+          }
+          for (int p = a.inc_rowptr[i]; p < a.inc_rowptr[i + 1]; ++p) {
+            const int64_t e = a.inc_edge[p];
+            const uint64_t f = (uint64_t)(e - e0g);
+            const double xf = f < (uint64_t)n ? x[f] : 0.0;
+            ti += a.ei[a.n_edges + e] == i ? xf : -xf;
+          }
+        }
+        s = tj - ti;
+      } else if (SMALL) {
         const int p0 = W.rp[v], p1 = W.rp[v + 1];
         s = (double)(p1 - p0) * x[v];
         for (int p = p0; p < p1; ++p) s -= x[W.nb[p]];
@@ -380,7 +448,7 @@ __device__ __forceinline__ void eig_pe_graph(const EigArgs& a, int g, int64_t n0
   }
   __syncthreads();
   if (tid == 0) {
-    a.lmax[g] = lam[m];
+    if (!EDGE) a.lmax[g] = lam[m];
     // clusters (dstein: ORTOL = 1e-3 ||T||) and the perturbation that keeps
     // equal eigenvalues' factorisations distinct
     const double eps = 2.220446049250313e-16;
@@ -422,7 +490,7 @@ __device__ __forceinline__ void eig_pe_graph(const EigArgs& a, int g, int64_t n0
   }
   // ---- 4. pe = Q y ----------------------------------------------------------------
   for (int v = tid; v < n; v += kEpThreads) {
-    float* out = a.pe + (n0 + v) * a.ldpe;
+    float* out = a.pe + ((EDGE ? e0g : n0) + v) * a.ldpe;
     for (int i = 1; i < k; ++i) {
       double s = 0.0;
       if (i < m) {
@@ -461,11 +529,48 @@ __global__ __launch_bounds__(kEpThreads) void k_eig_pe(EigArgs a) {
     }
     const int nnz = a.inc_rowptr[n0 + n] - a.inc_rowptr[n0];
     if (small_bytes(n, nnz, a.k) <= kEpLdsBytes)
-      eig_pe_graph<true>(a, (int)g, n0, n, ep_lds, red, lam, clus);
+      eig_pe_graph<true, false>(a, (int)g, n0, n, ep_lds, red, lam, clus);
     else
-      eig_pe_graph<false>(a, (int)g, n0, n,
-                          reinterpret_cast<char*>(a.ws + (int64_t)blockIdx.x * a.ws_per_graph),
-                          red, lam, clus);
+      eig_pe_graph<false, false>(a, (int)g, n0, n,
+                                 reinterpret_cast<char*>(a.ws + (int64_t)blockIdx.x * a.ws_per_graph),
+                                 red, lam, clus);
+    __syncthreads();  // the next graph reuses the LDS
+  }
+}
+
+// The edge entry: the same loop over graphs, n = the graph's edges.
+// a.max_nodes bounds the EDGES of a graph here (it sizes the workspace slice).
+__global__ __launch_bounds__(kEpThreads) void k_eig_pe_edges(EigArgs a) {
+  extern __shared__ __align__(16) char ep_lds[];
+  __shared__ double red[kEpThreads / 64];
+  __shared__ double lam[kEpMaxK + 1];
+  __shared__ int clus[kEpMaxK + 1];
+  for (int64_t g = blockIdx.x; g < a.n_graphs; g += gridDim.x) {
+    const int64_t e0 = a.edge_ptr[g];
+    const int64_t ne = a.edge_ptr[g + 1] - e0;
+    if (ne <= 0) continue;
+    if (ne > a.max_nodes) {
+      for (int64_t t = threadIdx.x; t < ne * (a.k - 1); t += kEpThreads)
+        a.pe[(e0 + t / (a.k - 1)) * a.ldpe + t % (a.k - 1)] = 0.0f;
+      if (threadIdx.x == 0 && a.err)
+        __hip_atomic_store(a.err, (unsigned)HLHGAT_DEVERR_EIGPE_SIZE, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+      continue;
+    }
+    const int n = (int)ne;
+    const int64_t n0 = a.node_ptr[g];
+    const int64_t nv = a.node_ptr[g + 1] - n0;
+    // the LDS layout holds the graph's node CSR: only when it is exactly the
+    // graph's 2 E entries (an edge without its graph's nodes goes the other way)
+    const bool lds = nv > 0 && nv <= 2ll * n &&
+                     (int64_t)a.inc_rowptr[n0 + nv] - a.inc_rowptr[n0] == 2ll * n &&
+                     small_bytes_edges(n, (int)nv, a.k) <= kEpLdsBytes;
+    if (lds)
+      eig_pe_graph<true, true>(a, (int)g, n0, n, ep_lds, red, lam, clus, e0, (int)nv);
+    else
+      eig_pe_graph<false, true>(a, (int)g, n0, n,
+                                reinterpret_cast<char*>(a.ws + (int64_t)blockIdx.x * a.ws_per_graph),
+                                red, lam, clus, e0, 0);
     __syncthreads();  // the next graph reuses the LDS
   }
 }
@@ -534,6 +639,74 @@ extern "C" int hlhgat_eig_pe(const int32_t* inc_rowptr, const int32_t* inc_edge,
   a.err = device_error_word();
   const int64_t grid = eig_pe_grid(n_graphs);
   hipLaunchKernelGGL(k_eig_pe, dim3((unsigned)grid), dim3(kEpThreads), kEpLdsBytes,
+                     as_stream(stream), a);
+  HLH_CHECK_LAUNCH();
+  return HLHGAT_OK;
+}
+
+// ---- the edge side -------------------------------------------------------------
+// The molecular datasets' edge PE is eig_pe(L1) (lib/Hodge_Dataset.py:458,
+// :587, :97-112): eigenvectors 1 .. k-1, ascending, of the E x E edge
+// Laplacian B1^T B1 (the reference's scaled L1 has the same vectors; column 0
+// is dropped as its [:, 1:k] does).  One launch for the batch, the node
+// entry's solver over the operator y = B1^T (B1 x):
+//   * edges are grouped by graph (edge_ptr [n_graphs + 1] beside node_ptr),
+//     i < j per edge, PairData offsets; pe is float32 [n_edges, ldpe] at the
+//     graph's edge rows;
+//   * L1's kernel is the cycle space (dimension E - n + c): an exactly
+//     degenerate cluster at 0 that costs one Lanczos restart per extra
+//     harmonic vector and is orthogonalised as any cluster (its basis is as
+//     arbitrary as LAPACK's); the nonzero spectrum is L0's; for a tree L1 is
+//     nonsingular and the dropped column is the mapped Fiedler vector;
+//   * columns >= E_g - 1 of a graph with E_g < k edges are zero, E_g = 0
+//     writes nothing, a graph with more than max_edges edges gets zero rows
+//     and HLHGAT_DEVERR_EIGPE_SIZE.
+// A graph whose basis and node CSR fit the LDS (small_bytes_edges: E <~ 120)
+// runs from it; a larger one from its workgroup's workspace slice, reading the
+// incidence CSR.
+extern "C" int64_t hlhgat_eig_pe_edges_workspace_bytes(int64_t n_graphs, int64_t max_edges, int k) {
+  return hlhgat_eig_pe_workspace_bytes(n_graphs, max_edges, k);
+}
+
+extern "C" int hlhgat_eig_pe_edges(const int32_t* inc_rowptr, const int32_t* inc_edge,
+                                   const int64_t* edge_index, int64_t n_edges, int64_t n_nodes,
+                                   const int64_t* node_ptr, const int64_t* edge_ptr,
+                                   int64_t n_graphs, int64_t max_edges, int k, float* pe,
+                                   int64_t ldpe, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  HLH_CHECK_ARG(k >= 2 && k <= kEpMaxK, "eig_pe_edges: k must be 2..%d", kEpMaxK);
+  HLH_CHECK_ARG(n_graphs >= 0 && n_nodes >= 0 && n_edges >= 0 && max_edges >= 0,
+                "eig_pe_edges: bad sizes");
+  HLH_CHECK_ARG(ldpe >= k - 1, "eig_pe_edges: ldpe < k - 1");
+  if (n_graphs == 0 || n_edges == 0) return HLHGAT_OK;
+  HLH_CHECK_ARG(inc_rowptr && inc_edge && edge_index && node_ptr && edge_ptr && pe && workspace,
+                "eig_pe_edges: NULL pointer");
+  HLH_CHECK_ARG(workspace_bytes >= hlhgat_eig_pe_edges_workspace_bytes(n_graphs, max_edges, k),
+                "eig_pe_edges: workspace too small");
+  static bool attr = false;
+  if (!attr) {
+    HLH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eig_pe_edges),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, kEpLdsBytes));
+    attr = true;
+  }
+  EigArgs a{};
+  a.inc_rowptr = inc_rowptr;
+  a.inc_edge = inc_edge;
+  a.ei = edge_index;
+  a.n_edges = n_edges;
+  a.node_ptr = node_ptr;
+  a.edge_ptr = edge_ptr;
+  a.k = k;
+  a.pe = pe;
+  a.ldpe = ldpe;
+  a.lmax = nullptr;
+  a.ws = reinterpret_cast<double*>(workspace);
+  a.ws_per_graph = per_graph_doubles(max_edges, k);
+  a.n_graphs = n_graphs;
+  a.max_nodes = max_edges;
+  a.err = device_error_word();
+  const int64_t grid = eig_pe_grid(n_graphs);
+  hipLaunchKernelGGL(k_eig_pe_edges, dim3((unsigned)grid), dim3(kEpThreads), kEpLdsBytes,
                      as_stream(stream), a);
   HLH_CHECK_LAUNCH();
   return HLHGAT_OK;

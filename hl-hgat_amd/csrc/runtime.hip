@@ -85,7 +85,7 @@ unsigned* device_error_word() {
 
 using namespace hlhgat;
 
-extern "C" int hlhgat_version(void) { return 110; }
+extern "C" int hlhgat_version(void) { return 111; }
 
 extern "C" int hlhgat_device_errors(unsigned* out) {
   HLH_CHECK_ARG(out, "device_errors: NULL pointer");

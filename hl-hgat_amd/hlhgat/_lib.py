@@ -76,6 +76,9 @@ SIGNATURES = {
     "hlhgat_eig_pe_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "hlhgat_eig_pe": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp,
                               c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "hlhgat_eig_pe_edges_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "hlhgat_eig_pe_edges": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
+                                    c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "hlhgat_hodge_row_sizes": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "hlhgat_hodge_build": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
                                    c_vp, c_vp, c_vp, c_i64, c_vp]),

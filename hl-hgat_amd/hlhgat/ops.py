@@ -666,6 +666,64 @@ def eig_pe(edge_index: torch.Tensor, node_counts, k: int, max_nodes: Optional[in
     return pe, lmax
 
 
+def _counts_ptr(counts, bound, dev, what):
+    """(ptr int64 [B + 1] on dev, bound) of host or device per-graph counts,
+    by eig_pe's rules: a device tensor needs the bound given."""
+    if torch.is_tensor(counts) and counts.is_cuda:
+        if bound is None:
+            raise ValueError(f"eig_pe_edges: max_edges is required with device {what} counts")
+        c = counts.to(torch.int64)
+    else:
+        host = [int(x) for x in counts]
+        mx = max(host) if host else 0
+        if bound is not None and int(bound) < mx:
+            raise ValueError(f"eig_pe_edges: max_edges {bound} < largest graph {mx}")
+        bound = mx if bound is None else int(bound)
+        c = torch.tensor(host, dtype=torch.int64).to(dev)
+    ptr = torch.zeros(c.numel() + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.cumsum(c, 0)
+    return ptr, bound
+
+
+def eig_pe_edges(edge_index: torch.Tensor, node_counts, edge_counts, k: int,
+                 max_edges: Optional[int] = None, n_nodes: Optional[int] = None):
+    """Edge-side eigenvector PE of every graph of a block-diagonal batch in one
+    launch (hlhgat_eig_pe_edges; the molecular datasets' eig_pe(L1),
+    lib/Hodge_Dataset.py:458, :587): edge_index int64 [2, E] (i < j, PairData
+    offsets, edges grouped by graph), node_counts / edge_counts per graph
+    (host sequences, or device tensors with max_edges given; n_nodes, the sum
+    of the node counts, spares a device read).  With device edge counts a graph
+    with more than max_edges edges gets zero rows and the kernel raises
+    HLHGAT_DEVERR_EIGPE_SIZE (check_device_errors).  Returns pe float32
+    [E, k - 1]: eigenvectors 1 .. k-1 of each graph's L1 = B1^T B1, ascending,
+    zero columns past a graph's own edge count."""
+    _req_dev(edge_index, "edge_index", torch.int64)
+    dev = edge_index.device
+    ei = edge_index.contiguous()
+    E = ei.size(1)
+    edge_ptr, max_edges = _counts_ptr(edge_counts, max_edges, dev, "edge")
+    if torch.is_tensor(node_counts) and node_counts.is_cuda:
+        node_ptr, _ = _counts_ptr(node_counts, 0, dev, "node")
+        N = int(node_ptr[-1].item()) if n_nodes is None else int(n_nodes)
+    else:
+        host = [int(c) for c in node_counts]
+        node_ptr, _ = _counts_ptr(host, None, dev, "node")
+        N = sum(host)
+    B = edge_ptr.numel() - 1
+    if node_ptr.numel() != B + 1:
+        raise ValueError("eig_pe_edges: node_counts and edge_counts differ in length")
+    inc = incidence(ei, N)
+    # rows the kernel does not own (edges past edge_ptr[-1]) stay zero
+    pe = torch.zeros(E, k - 1, dtype=torch.float32, device=dev)
+    wsb = int(LIB.hlhgat_eig_pe_edges_workspace_bytes(B, int(max_edges), k))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    check(LIB.hlhgat_eig_pe_edges(inc.rowptr.data_ptr(), inc.edge_ids.data_ptr() if E else None,
+                                  ei.data_ptr() if E else None, E, N, node_ptr.data_ptr(),
+                                  edge_ptr.data_ptr(), B, int(max_edges), k, pe.data_ptr(), k - 1,
+                                  ws.data_ptr(), wsb, _stream(ei)), "eig_pe_edges")
+    return pe
+
+
 def mlgc_device(edge_index: torch.Tensor, node_ptr: torch.Tensor, edge_ptr: torch.Tensor,
                 perm: torch.Tensor, weight: Optional[torch.Tensor] = None, one_way: bool = False,
                 prune_single: bool = False, drop_isolated: bool = False):
@@ -3631,8 +3689,9 @@ _DEVERR_TEXT = {
     _lib.DEVERR_BN_STATE: "BatchNorm: an arrival counter was found beyond its total (the "
                           "workspace was written by something else or shared by concurrent "
                           "launches); that launch's statistics are not trusted",
-    _lib.DEVERR_EIGPE_SIZE: "eig_pe: a graph has more nodes than max_nodes (which sized its "
-                            "workspace slice); its pe rows are zero and its lmax is 0",
+    _lib.DEVERR_EIGPE_SIZE: "eig_pe: a graph has more nodes than max_nodes (eig_pe_edges: more "
+                            "edges than max_edges), which sized its workspace slice; its pe "
+                            "rows are zero and its lmax is 0",
     _lib.DEVERR_MLGC_RANGE: "mlgc_device: an edge end outside its graph's node range, a perm "
                             "entry outside [0, n) or graph offsets that leave the arrays; the "
                             "offender was treated as absent",

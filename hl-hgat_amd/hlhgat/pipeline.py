@@ -56,7 +56,7 @@ from .hodge_dataset import (Batch, PairData, _h2d, collate, dense_to_sparse, gra
                             pool_tables)
 
 __all__ = ["SuperpixelPipeline", "to_undirected_min", "superpixel_raw", "BrainPipeline",
-           "brain_target"]
+           "brain_target", "MoleculePipeline", "to_undirected_min_nd", "molecule_raw"]
 
 
 def to_undirected_min(edge_index, attr, n: int):
@@ -739,3 +739,355 @@ class BrainPipeline:
         lv0.x_s = ops.fc_edges(prep, st["pair2edge"], self.E, tiles=st["tiles"])
         lv0.y = st["targets"].index_select(0, ids[:B])
         return [lv0] + list(levels[1:])
+
+
+# ----------------------------------------------------------------------------
+# molecules (ZINC, Peptides-func): process() for whole batches
+# ----------------------------------------------------------------------------
+def to_undirected_min_nd(edge_index, attr, n: int):
+    """to_undirected_min for attributes of any dtype with one or more columns
+    (Peptides' edge_attr is [E, 3]; lib/Hodge_Dataset.py:447, :576): both
+    directions, coalesced in (row, col) order, duplicates reduced by an
+    element-wise min.  Returns (int64 [2, E'], attr's dtype [E', ...])."""
+    ei = np.asarray(edge_index, dtype=np.int64)
+    a = np.asarray(attr)
+    r = np.concatenate([ei[0], ei[1]])
+    c = np.concatenate([ei[1], ei[0]])
+    aa = np.concatenate([a, a])
+    o = np.lexsort((c, r))
+    r, c, aa = r[o], c[o], aa[o]
+    first = np.ones(r.size, dtype=bool)
+    first[1:] = (r[1:] != r[:-1]) | (c[1:] != c[:-1])
+    starts = np.flatnonzero(first)
+    if starts.size == 0:
+        return np.zeros((2, 0), np.int64), aa[:0]
+    return np.stack([r[starts], c[starts]]), np.minimum.reduceat(aa, starts, axis=0)
+
+
+def molecule_raw(seed: int, n: int, kind: str = "zinc", edges=None):
+    """A raw molecule in the layout of PyG's ZINC / LRGB Peptides-func items:
+    x (zinc: atom class [n, 1] in 0..20; peptides: [n, 9] ints), edge_index
+    [2, 2 E] with BOTH directions in shuffled order, edge_attr (zinc: bond
+    class [2 E] in 1..3; peptides: [2 E, 3] ints), y (zinc [1]; peptides
+    [1, 10]).  The bonds are synthetic.molecule_edges(default_rng(seed), n),
+    or the given i < j edge list."""
+    from .synthetic import molecule_edges
+    rng = np.random.default_rng(seed)
+    ei = molecule_edges(rng, n) if edges is None else np.asarray(edges, np.int64).reshape(2, -1)
+    E = ei.shape[1]
+    d = PairData()
+    if kind == "zinc":
+        d.x = torch.from_numpy(rng.integers(0, 21, (n, 1)))
+        attr = rng.integers(1, 4, E)
+        d.y = torch.tensor([float(rng.normal())])
+    elif kind == "peptides":
+        d.x = torch.from_numpy(rng.integers(0, 10, (n, 9)))
+        attr = rng.integers(0, 4, (E, 3))
+        d.y = torch.from_numpy(rng.integers(0, 2, (1, 10)).astype(np.float32))
+    else:
+        raise ValueError(f"molecule_raw: kind must be 'zinc' or 'peptides' (got {kind!r})")
+    o = rng.permutation(2 * E)
+    d.edge_index = torch.from_numpy(np.concatenate([ei, ei[::-1]], axis=1)[:, o].copy())
+    d.edge_attr = torch.from_numpy(np.concatenate([attr, attr])[o])
+    return d
+
+
+def _coarse_level(ei1_d, n1_d, m1_d, N1, E1, sizes1, dev) -> Batch:
+    """The collated coarse level of one MLGC step on the device: ones
+    features and its own Hodge Laplacians (lib/Hodge_Dataset.py:275-294), as
+    SuperpixelPipeline._levels_finish builds it."""
+    from . import ops
+    c_t, c_wt, c_s, c_ws, _ = ops.hodge_build(ei1_d, n1_d, sizes=sizes1)
+    lv1 = Batch()
+    lv1.num_graphs = int(n1_d.numel())
+    lv1.x_t = torch.ones(N1, 1, device=dev)
+    lv1.x_s = torch.ones(E1, 1, device=dev)
+    lv1.edge_index_t, lv1.edge_weight_t = c_t, c_wt
+    lv1.edge_index_s, lv1.edge_weight_s = c_s, c_ws
+    lv1.edge_index = ei1_d
+    lv1.num_node1, lv1.num_edge1 = n1_d, m1_d
+    lv1.num_nodes = N1
+    lv1.hodge_sorted = {"edge_index_s": True, "edge_index_t": True}
+    lv1.l1_factor = False
+    lv1._mark()
+    return lv1
+
+
+class MoleculePipeline:
+    """The molecular datasets' process() (ZINC_HG_BM_par1_EigPE.process,
+    lib/Hodge_Dataset.py:442-477; Peptides_Func_EigPE.process, :571-605) for
+    whole batches on the device, and Peptides_Func_EigPE_MLGC.get's per-access
+    MLGC (:628-650).
+
+    raw: samples with x, edge_index, edge_attr, y as PyG's ZINC / LRGB
+      datasets give them (molecule_raw).
+    kind: "zinc" (x_t = [one_hot(x, 21), pe], x_s = [one_hot(attr - 1, 3), pe],
+      y = (y - 0.0153) / 2.0109) or "peptides" (the 9 / 3 raw columns cast to
+      float, then the PE).
+    keig: the dataset's keig: each side is fixed + keig - 1 wide, the widths
+      get() cuts or pads to (:425-440, :554-569); columns past a small
+      graph's size are zero.  No sign flip is applied: ops / nn.PESignFlip
+      does that per replay.
+
+    The reference runs three dense LAPACK eighs per graph at batch size 1;
+    batch() runs one hlhgat_eig_pe launch (node PE and lambda_max), one
+    hlhgat_eig_pe_edges launch (edge PE: eigenvectors of L1 = B1^T B1) and one
+    hlhgat_hodge_build with that lambda_max for the whole batch.  The sizes of
+    the Laplacians come from the host degrees, so nothing waits on the device.
+    device="cpu" runs the reference's arithmetic graph by graph (dense float32
+    eigh) -- the restatement the golden test pins
+    (tests/golden/make_golden_molecule.py)."""
+
+    FIXED = {"zinc": (21, 3), "peptides": (9, 3)}
+    PROFILE = False
+    _tick = SuperpixelPipeline._tick
+    _segments = staticmethod(SuperpixelPipeline._segments)
+
+    def __init__(self, raw: Sequence, kind: str = "zinc", keig: int = 16):
+        if kind not in self.FIXED:
+            raise ValueError(f"MoleculePipeline: kind must be 'zinc' or 'peptides' (got {kind!r})")
+        if not 2 <= int(keig) <= 64:
+            raise ValueError("MoleculePipeline: keig must be 2..64")
+        self.kind, self.keig = kind, int(keig)
+        self.ft, self.fs = self.FIXED[kind]
+        self.n = np.array([int(g.x.shape[0]) for g in raw], dtype=np.int64)
+        eis, xts, xss, ys = [], [], [], []
+        for g, n in zip(raw, self.n):
+            # to_undirected(reduce='min') and the i < j half (:447-450)
+            ei, a = to_undirected_min_nd(g.edge_index, g.edge_attr, int(n))
+            keep = ei[0] < ei[1]
+            ei, a = ei[:, keep], torch.from_numpy(np.ascontiguousarray(a[keep]))
+            x = torch.as_tensor(np.asarray(g.x))
+            if kind == "zinc":
+                xs = torch.nn.functional.one_hot(a.long() - 1, num_classes=3).to(torch.float)
+                xt = torch.nn.functional.one_hot(x.long().reshape(-1), num_classes=21).to(torch.float)
+                y = (torch.as_tensor(g.y).to(torch.float) - 0.0153) / 2.0109
+            else:
+                xs, xt = a.to(torch.float).reshape(-1, 3), x.to(torch.float).reshape(-1, 9)
+                y = torch.as_tensor(g.y).to(torch.float)
+            eis.append(ei)
+            xts.append(xt.numpy())
+            xss.append(xs.numpy())
+            ys.append(y)
+        self.ei, self.y = eis, ys
+        self.m = np.array([e.shape[1] for e in eis], dtype=np.int64)
+        self.n_off = np.concatenate([[0], np.cumsum(self.n)]).astype(np.int64)
+        self.e_off = np.concatenate([[0], np.cumsum(self.m)]).astype(np.int64)
+        self.ei_all = np.concatenate(eis, axis=1) if eis else np.zeros((2, 0), np.int64)
+        self.xt_all = np.concatenate(xts) if xts else np.zeros((0, self.ft), np.float32)
+        self.xs_all = np.concatenate(xss) if xss else np.zeros((0, self.fs), np.float32)
+        self.y_dim = int(ys[0].numel()) if ys else 1
+        self.y_all = (torch.stack([y.reshape(-1) for y in ys]).numpy() if ys
+                      else np.zeros((0, 1), np.float32))
+
+    def __len__(self) -> int:
+        return len(self.n)
+
+    @property
+    def widths(self):
+        """(x_t width, x_s width) = fixed + keig - 1."""
+        return self.ft + self.keig - 1, self.fs + self.keig - 1
+
+    # -- device="cpu": the reference's arithmetic ----------------------------------
+    def _graph_host(self, i: int) -> PairData:
+        from scipy.linalg import eigh
+        ei, n = self.ei[i], int(self.n[i])
+        L0, L1, _, _ = hodge_laplacians(ei, n)
+
+        def pe(L, rows):
+            out = np.zeros((rows, self.keig - 1), np.float32)
+            if rows:
+                vals, vecs = eigh(L.numpy())
+                v = np.real(vecs[:, vals.argsort()])[:, 1:self.keig]
+                out[:, :v.shape[1]] = v
+            return out
+
+        n0, e0 = self.n_off[i], self.e_off[i]
+        x_t = np.concatenate([self.xt_all[n0:n0 + n], pe(L0, n)], axis=1)
+        x_s = np.concatenate([self.xs_all[e0:e0 + ei.shape[1]], pe(L1, ei.shape[1])], axis=1)
+        eit, ewt = dense_to_sparse(L0)
+        eis, ews = dense_to_sparse(L1)
+        g = PairData(x_s=torch.from_numpy(x_s), edge_index_s=eis, edge_weight_s=ews,
+                     x_t=torch.from_numpy(x_t), edge_index_t=eit, edge_weight_t=ewt, y=self.y[i])
+        g.edge_index = torch.from_numpy(ei)
+        g.num_node1, g.num_edge1, g.num_nodes = n, int(ei.shape[1]), n
+        g._hodge_sorted = True
+        return g
+
+    # -- the batch -------------------------------------------------------------------
+    def batch(self, idx, device="cuda") -> Batch:
+        """process() of the molecules idx as one collated Batch."""
+        idx = np.asarray([int(i) for i in idx], dtype=np.int64)
+        B = idx.size
+        if B == 0 or idx.min() < 0 or idx.max() >= len(self):
+            raise ValueError(f"MoleculePipeline: molecules {idx.tolist()} outside [0, {len(self)})")
+        self._tick(None)
+        ns, E_g = self.n[idx], self.m[idx]
+        eidx = self._segments(self.e_off[idx], E_g)
+        ei = self.ei_all[:, eidx]
+        if str(device) == "cpu":
+            b = collate([self._graph_host(int(i)) for i in idx], check_hodge=False)
+            b._mol_host = (ns, E_g, ei)
+            self._tick("host: reference arithmetic")
+            return b
+        from . import ops
+        dev = torch.device(device)
+        N, E = int(ns.sum()), int(E_g.sum())
+        n_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        gid_e = np.repeat(np.arange(B), E_g)
+        ei_b = ei + n_off[gid_e]  # block-diagonal batch (PairData offsets)
+        nodes = self._segments(self.n_off[idx], ns)
+        ints = [ei_b.reshape(-1), ns, E_g]
+        flts = [self.xt_all[nodes].reshape(-1), self.xs_all[eidx].reshape(-1),
+                self.y_all[idx].reshape(-1)]
+        idev = _h2d(np.concatenate(ints), dev)
+        fdev = _h2d(np.concatenate(flts), dev)
+        ei_d, ns_d, Eg_d = idev[:2 * E].view(2, E), idev[2 * E:2 * E + B], idev[2 * E + B:]
+        xt_f = fdev[:N * self.ft].view(N, self.ft)
+        xs_f = fdev[N * self.ft:N * self.ft + E * self.fs].view(E, self.fs)
+        y_d = fdev[N * self.ft + E * self.fs:]
+        self._tick("upload")
+        k = self.keig
+        pe_t, lam64 = ops.eig_pe(ei_d, ns_d, k, max_nodes=int(ns.max()), n_nodes=N)
+        self._tick("eig_pe + lambda_max")
+        pe_s = ops.eig_pe_edges(ei_d, ns_d, Eg_d, k, max_edges=int(E_g.max()), n_nodes=N)
+        self._tick("eig_pe_edges")
+        ei_t, w_t, ei_s, w_s, _ = ops.hodge_build(ei_d, ns_d, lmax=lam64.to(torch.float32),
+                                                  sizes=(N,) + SuperpixelPipeline._nnz(ei_b, N))
+        self._tick("Hodge build")
+        wt, ws = self.widths
+        b = Batch()
+        b.num_graphs = B
+        b.x_t = torch.empty(N, wt, device=dev)
+        b.x_t[:, :self.ft] = xt_f
+        b.x_t[:, self.ft:] = pe_t
+        b.x_s = torch.empty(E, ws, device=dev)
+        b.x_s[:, :self.fs] = xs_f
+        b.x_s[:, self.fs:] = pe_s
+        b.edge_index_t, b.edge_weight_t = ei_t, w_t
+        b.edge_index_s, b.edge_weight_s = ei_s, w_s
+        b.edge_index = ei_d
+        b.y = y_d.clone() if self.y_dim == 1 else y_d.view(B, self.y_dim).clone()
+        b.num_node1, b.num_edge1 = ns_d, Eg_d
+        b.num_nodes = N
+        b.hodge_sorted = {"edge_index_s": True, "edge_index_t": True}
+        b.l1_factor = False
+        b._mark()
+        b._mol_host = (ns, E_g, ei)
+        self._tick("features")
+        return b
+
+    # -- the stored dataset --------------------------------------------------------
+    def graphs(self, device="cuda", chunk: int = 1024) -> List[PairData]:
+        """The stored dataset process() writes, as per-graph host PairData
+        (ready for PackedGraphs / GraphLoader / shard_graphs): device batches
+        of `chunk` molecules cut back into graphs.  An eigenvector's sign, and
+        the basis inside a cluster of equal eigenvalues, follow the graph's
+        place in its launch (the solver's start vectors are seeded by it), so
+        another chunk size gives other, equally valid signs; everything else
+        is the same bits."""
+        if str(device) == "cpu":
+            return [self._graph_host(i) for i in range(len(self))]
+        out = []
+        for c0 in range(0, len(self), int(chunk)):
+            idx = np.arange(c0, min(c0 + int(chunk), len(self)))
+            b = self.batch(idx, device)
+            ns, E_g, ei = b._mol_host
+            x_t, x_s, y = b.x_t.cpu(), b.x_s.cpu(), b.y.cpu()
+            eit, wt, eis, ws = (t.cpu() for t in (b.edge_index_t, b.edge_weight_t,
+                                                  b.edge_index_s, b.edge_weight_s))
+            n_off = np.concatenate([[0], np.cumsum(ns)])
+            e_off = np.concatenate([[0], np.cumsum(E_g)])
+            # entries of L0 / L1 per graph, from the degrees (SuperpixelPipeline._nnz)
+            gid_e = np.repeat(np.arange(idx.size), E_g)
+            deg = np.bincount((ei + n_off[gid_e]).reshape(-1), minlength=int(n_off[-1]))
+            gid_n = np.repeat(np.arange(idx.size), ns)
+            z_t = np.bincount(gid_n, weights=(deg > 0), minlength=idx.size).astype(np.int64) + 2 * E_g
+            z_s = np.bincount(gid_n, weights=deg * deg, minlength=idx.size).astype(np.int64) - E_g
+            t_off = np.concatenate([[0], np.cumsum(z_t)])
+            s_off = np.concatenate([[0], np.cumsum(z_s)])
+            for g in range(idx.size):
+                n0, n1, e0, e1 = n_off[g], n_off[g + 1], e_off[g], e_off[g + 1]
+                p = PairData(x_s=x_s[e0:e1].clone(),
+                             edge_index_s=(eis[:, s_off[g]:s_off[g + 1]] - e0).contiguous(),
+                             edge_weight_s=ws[s_off[g]:s_off[g + 1]].clone(),
+                             x_t=x_t[n0:n1].clone(),
+                             edge_index_t=(eit[:, t_off[g]:t_off[g + 1]] - n0).contiguous(),
+                             edge_weight_t=wt[t_off[g]:t_off[g + 1]].clone(),
+                             y=y[g:g + 1].clone())
+                p.edge_index = torch.from_numpy(np.ascontiguousarray(ei[:, e0:e1]))
+                p.num_node1, p.num_edge1, p.num_nodes = int(ns[g]), int(E_g[g]), int(ns[g])
+                p._hodge_sorted = True
+                out.append(p)
+        return out
+
+    # -- per-access MLGC -------------------------------------------------------------
+    def coarsen(self, batch: Batch, seed: int = 0, perms=None, mlgc: str = "device") -> List[Batch]:
+        """Peptides_Func_EigPE_MLGC.get's MLGC (:633-637) for a collated
+        level-0 batch (batch()): graclus node orders per graph drawn from
+        `seed` (perms: explicit orders), the fine -> coarse maps by
+        ops.mlgc_device (mlgc="device": one device -> host read, the coarse
+        sizes) or hodge_dataset.mlgc_batch_flat (mlgc="host"); returns [lv0,
+        lv1]: lv0 = the batch with c_node / c_edge as a new column 0 of x_t /
+        x_s, lv1 the coarse level (ones features, its own Laplacians).  The
+        two routes agree bit for bit given the same orders.  A batch on the
+        host takes the reference's arithmetic graph by graph."""
+        import copy
+        if mlgc not in ("host", "device"):
+            raise ValueError(f"MoleculePipeline: mlgc must be 'host' or 'device' (got {mlgc!r})")
+        host = getattr(batch, "_mol_host", None)
+        if host is None:  # a batch collated elsewhere: its counts and edges are read back
+            ns = np.asarray(batch.num_node1.cpu(), np.int64)
+            E_g = np.asarray(batch.num_edge1.cpu(), np.int64)
+            ei = np.asarray(batch.edge_index.cpu(), np.int64)[:, :int(E_g.sum())]
+            ei = ei - np.repeat(np.concatenate([[0], np.cumsum(ns)[:-1]]), E_g)
+        else:
+            ns, E_g, ei = host
+        B = ns.size
+        if perms is None:
+            rng = np.random.default_rng(seed)
+            perms = [rng.permutation(int(n)) for n in ns]
+        perm = np.concatenate([np.asarray(p, np.int64) for p in perms])
+        dev = batch.x_t.device
+        lv0 = copy.copy(batch)
+        n_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        e_off = np.concatenate([[0], np.cumsum(E_g)]).astype(np.int64)
+        if dev.type == "cpu" or mlgc == "host":
+            mg = mlgc_batch_flat(ei, E_g, ns, perm)
+            c_node = torch.from_numpy(mg.c_node.astype(np.float32))
+            c_edge = torch.from_numpy(mg.c_edge)
+            if dev.type == "cpu":
+                from .hodge_dataset import _mlgc_level
+                lv1 = collate([_mlgc_level(e1, n1) for _, _, e1, n1 in mg.per_graph()],
+                              check_hodge=False)
+            else:
+                n1, m1 = mg.cn, mg.cm
+                o1 = np.concatenate([[0], np.cumsum(n1)]).astype(np.int64)
+                cidx = self._segments(e_off[:-1], m1)
+                ei1 = mg.ce[:, cidx] + o1[np.repeat(np.arange(B), m1)]
+                N1, E1 = int(o1[-1]), int(ei1.shape[1])
+                idev = _h2d(np.concatenate([ei1.reshape(-1), n1, m1]), dev)
+                fdev = _h2d(np.concatenate([mg.c_node.astype(np.float32), mg.c_edge]), dev)
+                c_node, c_edge = fdev[:n_off[-1]], fdev[n_off[-1]:]
+                lv1 = _coarse_level(idev[:2 * E1].view(2, E1), idev[2 * E1:2 * E1 + B],
+                                    idev[2 * E1 + B:], N1, E1,
+                                    (N1,) + SuperpixelPipeline._nnz(ei1, N1), dev)
+        else:
+            from . import ops
+            ptrs = _h2d(np.concatenate([perm, n_off, e_off]), dev)
+            N = int(n_off[-1])
+            perm_d, nptr_d, eptr_d = ptrs[:N], ptrs[N:N + B + 1], ptrs[N + B + 1:]
+            r = ops.mlgc_device(batch.edge_index, nptr_d, eptr_d, perm_d)
+            n1_d, m1_d = r.cn, r.cm
+            # the one read-back: the coarse level's sizes
+            N1, E1 = (int(v) for v in torch.stack([n1_d.sum(), m1_d.sum()]).cpu())
+            gid_c = torch.repeat_interleave(torch.arange(B, device=dev), m1_d, output_size=E1)
+            c_off = torch.cumsum(m1_d, 0) - m1_d
+            o1 = torch.cumsum(n1_d, 0) - n1_d
+            src = torch.arange(E1, device=dev) - c_off[gid_c] + eptr_d[:-1][gid_c]
+            ei1_d = r.ce[:, src] + o1[gid_c]
+            c_node, c_edge = r.c_node, r.c_edge
+            lv1 = _coarse_level(ei1_d, n1_d, m1_d, N1, E1, None, dev)
+        lv0.x_t = torch.cat([c_node.view(-1, 1), batch.x_t], dim=1)
+        lv0.x_s = torch.cat([c_edge.view(-1, 1), batch.x_s], dim=1)
+        return [lv0, lv1]

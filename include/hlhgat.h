@@ -499,6 +499,29 @@ int hlhgat_eig_pe(const int32_t* inc_rowptr, const int32_t* inc_edge, const int6
                   int64_t n_edges, int64_t n_nodes, const int64_t* node_ptr, int64_t n_graphs,
                   int64_t max_nodes, int k, float* pe, int64_t ldpe, double* lmax,
                   void* workspace, int64_t workspace_bytes, void* stream);
+/* hlhgat_eig_pe_edges: the EDGE-side eigenvector PE of every graph of the
+ * batch in one launch -- the molecular datasets' eig_pe(L1)
+ * (lib/Hodge_Dataset.py:458, :587, with eig_pe at :97-112): pe[e][0 .. k-2]
+ * (float32, row stride ldpe, at the graph's edge rows) = eigenvectors
+ * 1 .. k-1, ascending, of the unscaled L1 = B1^T B1 (the same vectors as the
+ * reference's scaled L1; column 0 dropped as its [:, 1:k] does).  The same
+ * solver as hlhgat_eig_pe over the operator y = B1^T (B1 x).  The batch's
+ * edges are grouped by graph: edge_ptr [n_graphs + 1] beside node_ptr, i < j
+ * per edge, PairData offsets.  L1's kernel is the cycle space (dimension
+ * E - n + c): an exactly degenerate cluster at 0 whose basis is arbitrary
+ * (the reference's is LAPACK's); the nonzero spectrum is L0's; a tree's L1 is
+ * nonsingular.  2 <= k <= 64; columns >= E_g - 1 of a graph with E_g < k
+ * edges are zero; E_g = 0 writes nothing; a graph with more than max_edges
+ * edges (which size the workspace slice) gets zero rows and
+ * HLHGAT_DEVERR_EIGPE_SIZE, nothing else is touched.  Deterministic: a second
+ * launch is bitwise equal.  Vectors are defined up to sign, and up to rotation
+ * inside a cluster of equal eigenvalues. */
+int64_t hlhgat_eig_pe_edges_workspace_bytes(int64_t n_graphs, int64_t max_edges, int k);
+int hlhgat_eig_pe_edges(const int32_t* inc_rowptr, const int32_t* inc_edge,
+                        const int64_t* edge_index, int64_t n_edges, int64_t n_nodes,
+                        const int64_t* node_ptr, const int64_t* edge_ptr, int64_t n_graphs,
+                        int64_t max_edges, int k, float* pe, int64_t ldpe, void* workspace,
+                        int64_t workspace_bytes, void* stream);
 /* Row sizes of L0 (deg(v) + 1, 0 for an isolated node) and L1 (deg(i) +
  * deg(j) - 1); exclusive-scan them into the row pointers. */
 int hlhgat_hodge_row_sizes(const int32_t* inc_rowptr, const int64_t* edge_index,
@@ -1191,7 +1214,8 @@ int hlhgat_copy2d_batched(int n, const float* const* src, const int64_t* lds,
 /* hlhgat_collect_rows: the rows did not fit the buffer; none was appended */
 #define HLHGAT_DEVERR_METER_FULL 16u
 /* hlhgat_eig_pe: a graph has more nodes than the caller's max_nodes (which
- * sized its workspace slice); its pe rows are zero and its lmax is 0 */
+ * sized its workspace slice); its pe rows are zero and its lmax is 0.
+ * hlhgat_eig_pe_edges: more edges than max_edges; its pe rows are zero */
 #define HLHGAT_DEVERR_EIGPE_SIZE 32u
 /* hlhgat_mlgc_device: an edge end outside its graph's node range, a perm entry
  * outside [0, n), or graph offsets that leave the arrays / the workspace; the
